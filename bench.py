@@ -30,6 +30,12 @@ Memory is reported as measured: ``peak_gpu_mem_gb`` (allocator high-water),
 ``peak_device_used_gb`` (``hipMemGetInfo`` total - free sampled every 10 ms by a thread during every
 step: context, code objects, RCCL buffers and allocator slack included),
 ``host_pinned_gb`` and ``host_peak_rss_gb``.
+
+A plain run sets up, warms up, times ``--steps`` passes and prints the result
+line; ``--dump-outputs DIR`` also writes the last timed pass's scores as
+``DIR/scores_<prompt>.npy`` (float32; weights and prompts are seeded, so two
+builds run with the same arguments can be compared array for array).
+``--full`` is where anything measured beyond the headline figure belongs.
 """
 from __future__ import annotations
 
@@ -43,6 +49,8 @@ import sys
 import time
 
 import numpy as np
+
+T_PROC = time.perf_counter()      # (close to) process start: the set-up log line counts from here
 
 METRIC = "tokens/sec + peak GPU mem, Llama-2-70B layer_num_per_shard=1 at 1/2/4/8 MI355X"
 
@@ -147,11 +155,45 @@ def parse(argv=None):
     ap.add_argument("--o-direct", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's scores (what a caller of the runner gets: "
+                         "one array per prompt) as DIR/<name>.npy in float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure.  A plain run "
+                         "already does only set-up, warm-up, the timed steps and the result line (its memory "
+                         "figures are sampled during those steps and are part of the headline), so today "
+                         "this adds nothing")
     ap.add_argument("--cpu", action="store_true", help="CPU/gloo rehearsal of the same code path (tests only)")
     ap.add_argument("--loopback-ranks", type=int, default=0,
                     help="model-parallel rehearsal on ONE device: R pipeline ranks as threads over the loopback "
                          "comm (device copies instead of RCCL), the real StageInbox / program; not a scaling number")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, outs, prefix: str = "", budget: int = DUMP_BUDGET_BYTES) -> int:
+    """--dump-outputs: write a step's scores (one array per prompt, in prompt order; None where this
+    rank does not own the result) as ``d/<prefix>scores_<i>.npy`` in float32.  Arrays that together
+    exceed ``budget`` bytes are cut to a fixed, seeded sample of their flattened elements (the same
+    indices on every run), each array keeping a share in proportion to its size."""
+    os.makedirs(d, exist_ok=True)
+    arrs = [(i, np.asarray(o)) for i, o in enumerate(outs or []) if o is not None]
+    total = sum(x.size for _, x in arrs) * 4
+    written = 0
+    for i, x in arrs:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if total > budget:
+            keep = max(1, int(x.size * (budget / total)))
+            idx = np.sort(np.random.default_rng(1234 + i).choice(x.size, size=keep, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{prefix}scores_{i:04d}.npy"), x)
+        written += x.nbytes
+    return written
 
 
 def spawn_ranks(a, argv) -> int:
@@ -254,6 +296,8 @@ def loopback_main(a) -> int:
     tokens = res[0][1]["tokens"]
     owner = [v[2] for v in res.values() if v[2] and v[2][0] is not None]
     finite = bool(owner) and all(np.isfinite(o.astype(np.float32)).all() for o in owner[0])
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, owner[0] if owner else [])
     rx = {r: {k: v for k, v in res[r][1].items() if k.startswith("rx_")} for r in range(R)}
     ok, _ = simulate_single_queue({r: hub.log[r] for r in range(R)})
     out = {"metric": "model-parallel rehearsal on one device (loopback ranks; not a scaling number)",
@@ -321,6 +365,7 @@ def main(argv=None):
     from flexible_llm_sharding_amd.utils.tokenizer import clear_prefix_ids, load_tokenizer, write_synthetic_tokenizer
 
     from flexible_llm_sharding_amd import knobs
+    t_imports = time.perf_counter() - T_PROC
     # the fused-norm GEMMs read W_qkv / W_gate-up with the RMSNorm weights folded in: once into the
     # pinned host image as it is built, before timing (--norm-fold prefolded, the default:
     # HostStore.fold_norms), or as each layer lands in HBM on every pass, on the copy stream, from the
@@ -425,6 +470,7 @@ def main(argv=None):
         runner.ctx.attn_rows = a.attn_rows
     if runner.vram_plan:
         log(rank, f"[bench] --max-vram-gb {a.max_vram_gb}: {runner.vram_plan}")
+    log(rank, f"[bench] set-up {time.perf_counter() - T_PROC:.1f}s since start (imports {t_imports:.1f}s)")
     sampler = DeviceSampler(dev) if not a.cpu else None
     if not a.cpu:
         torch.cuda.reset_peak_memory_stats(dev)
@@ -488,6 +534,10 @@ def main(argv=None):
         if o is not None:
             h.update(np.ascontiguousarray(o).tobytes())
     digests = comm.all_gather_object(h.hexdigest()[:16])
+    if a.dump_outputs:
+        # every rank writes the scores it holds (data parallel: its own prompts'), sharing the budget
+        nb = dump_outputs(a.dump_outputs, outs, "" if world == 1 else f"rank{rank}_", DUMP_BUDGET_BYTES // world)
+        log(rank, f"[bench] --dump-outputs {a.dump_outputs}: {nb / 1e6:.1f} MB")
     # which ranks / devices took part (the process group the collectives actually ran on)
     import torch.distributed as dist
     pg_world = dist.get_world_size() if dist.is_initialized() else 1
@@ -535,6 +585,7 @@ def main(argv=None):
                 json.dump(out, f, indent=1)
     runner.close()
     comm.destroy()
+    log(rank, f"[bench] done {time.perf_counter() - T_PROC:.1f}s since start ({elapsed:.1f}s in the timed steps)")
     return 0
 
 

@@ -68,6 +68,39 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     assert out["config"]["parallelism"].startswith("dp3") and out["scores_finite"] is True
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs DIR writes the last timed step's scores, one float32 array per prompt; the
+    inputs are seeded, so a second run (here with --full) writes the same arrays."""
+    import numpy as np
+    out = _bench(1, ["--dump-outputs", str(tmp_path / "a")], tmp_path)
+    out2 = _bench(1, ["--dump-outputs", str(tmp_path / "b"), "--full"], tmp_path)
+    assert out["steps"] == 2 and out["scores_sha1"] == out2["scores_sha1"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == [f"scores_{i:04d}.npy" for i in range(3)] == sorted(os.listdir(tmp_path / "b"))
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and x.shape == (5, 1, 512) and np.isfinite(x).all()
+        assert np.allclose(x.sum(-1), 1.0, atol=2e-2)          # rows are probabilities
+        assert np.array_equal(x, y)
+
+
+def test_bench_dump_outputs_sample_is_fixed(tmp_path):
+    """Outputs above the byte budget are cut to the same seeded sample on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    outs = [np.arange(1000, dtype=np.float16).reshape(10, 100), None, np.ones((3, 50), np.float16)]
+    n = bench.dump_outputs(str(tmp_path / "s1"), outs, budget=1150 * 4 // 2)
+    bench.dump_outputs(str(tmp_path / "s2"), outs, budget=1150 * 4 // 2)
+    assert n <= 1150 * 4 // 2 and sorted(os.listdir(tmp_path / "s1")) == ["scores_0000.npy", "scores_0002.npy"]
+    a, b = np.load(tmp_path / "s1" / "scores_0000.npy"), np.load(tmp_path / "s2" / "scores_0000.npy")
+    assert a.dtype == np.float32 and a.shape == (500,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)                               # distinct elements, in order
+
+
 @pytest.mark.parametrize("world", [1, 2])
 def test_bench_stream_weights(tmp_path, world):
     """--weights stream: per-layer files written once, re-read every pass (DP: each rank its 1/G
