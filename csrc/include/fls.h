@@ -139,6 +139,16 @@ int fls_attention(const void* qkv, void* out, const int* work, int n_items, int 
                   int n_kv_heads, int head_dim, int ld_qkv, int ld_out, float scale, const void* kv0,
                   int ld_kv0, const int* seg_lo, int q_block, const int* work2, const int* r2win,
                   void* ws, unsigned long long ws_bytes, int n_rows, fls_stream_t s);
+// sliding-window attention: fls_attention with a per-row lower bound on range 0.  r0_lo ([T] int32):
+// the first range-0 key a row sees, relative to the range start, in [0, r0_len] (r0_len: none);
+// r0_item (int32 x2 per item): min and max of r0_lo over the item's rows - range 0 is walked from
+// the 64-key tile of the min and masked per row below the max.  The window of ranges 1 and 2 is in
+// seg_lo and r2win (first visible row of each).  Both arrays are required.
+int fls_attention_window(const void* qkv, void* out, const int* work, int n_items, int n_q_heads,
+                         int n_kv_heads, int head_dim, int ld_qkv, int ld_out, float scale, const void* kv0,
+                         int ld_kv0, const int* seg_lo, int q_block, const int* work2, const int* r2win,
+                         void* ws, unsigned long long ws_bytes, int n_rows, const int* r0_lo,
+                         const int* r0_item, fls_stream_t s);
 int fls_headnorm_rope(void* x, int ldx, int rows, int n_q, int n_k, const void* qn, const void* kn, const int* pos,
                       const float* cos_t, const float* sin_t, int hd, float eps, fls_stream_t s);
 int fls_rmsnorm(const void* x, const void* w, void* y, const int* row_idx, int rows, int H,

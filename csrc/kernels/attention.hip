@@ -109,13 +109,21 @@ __device__ __forceinline__ void lds_wait4(half4& a, half4& b, half4& c, half4& d
 // tiles and writes its unnormalised O, running max and row sum in fp32 to `part`
 // ([rows][splits][nh] x (HD + 2)); attn_split_combine merges the slices.  For grids with fewer
 // blocks than CUs (few prompts with long contexts), which otherwise leave most CUs idle.
-template <int HD, int HPB, int WPH, bool R2, bool SPL = false>
+// WIN (sliding window): r0_lo[row] is the first range-0 key the row sees (relative to the range
+// start, in [0, r_len0]; r_len0: none) and r0_item[item] = {min, max} of it over the item's rows.
+// Range 0 is walked from the 64-key tile holding the min (tiles stay at multiples of 64 keys from
+// the range start; no tile at all when the min is past the last visible key), and its tiles that
+// start below the max are masked per row.  Ranges 1 and 2 carry the window in seg_lo / r2win.  A
+// tile that is fully masked for a row leaves the row's m, l and O bitwise alone (mx = -inf keeps
+// m_run, P = 0), so which masked tiles an item walks does not change a row's bits.
+template <int HD, int HPB, int WPH, bool R2, bool SPL = false, bool WIN = false>
 __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __restrict__ qkv, half_t* __restrict__ out,
                                                     const int* __restrict__ work, const int* __restrict__ seg_lo,
                                                     int nh, int nkv, int ld_qkv, int ld_out, float scale_log2,
                                                     const half_t* __restrict__ kv0, int ld_kv0,
                                                     const int* __restrict__ work2, const int* __restrict__ r2win,
-                                                    float* __restrict__ part) {
+                                                    float* __restrict__ part, const int* __restrict__ r0_lo,
+                                                    const int* __restrict__ r0_item) {
   static_assert(!SPL || R2, "split-KV is built for the range-2 (suffix K/V reuse) kernel only");
   constexpr int NT_ = 64 * WPH * HPB;
   constexpr int NS = HD / 32;               // k-steps of QK^T
@@ -136,13 +144,24 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
   const int* wi = work + blockIdx.x * 8;
   const int q_start = wi[0], q_len = wi[1], q_off = wi[2];
   if (q_len <= 0) return;                   // padding item (bucketed graph replays); block-uniform
-  const int r_start0 = wi[3], r_len0 = wi[4], r_causal0 = wi[5];
+  const int r_start0_ = wi[3], r_len0_ = wi[4], r_causal0 = wi[5];
   const int r_start1 = wi[6], r_len1 = wi[7];
-  const int kend0 = r_len0 <= 0 ? 0 : (r_causal0 ? min(r_len0, q_off + q_len) : r_len0);
+  const int kend0_ = r_len0_ <= 0 ? 0 : (r_causal0 ? min(r_len0_, q_off + q_len) : r_len0_);
+  // WIN: range 0 is re-based at its first walked tile, shift0 keys (a multiple of KT) behind the
+  // range start: the tile loop, the loader and the masks below then see an ordinary range 0 whose
+  // row bounds (and causal compare) are shifted by as much; the re-based start stays inside the
+  // range (range 2 is read at a row offset from it).  No range-0 tile at all (skip0) when the
+  // item's first visible key is past the last visible one.  shift0 and skip0 are constants when
+  // !WIN, so the unwindowed instantiations compile to the code they always had.
+  const int first0 = WIN ? min(max(r0_item[blockIdx.x * 2], 0), max(r_len0_, 0)) : 0;
+  const bool skip0 = WIN && first0 >= kend0_;
+  const int shift0 = WIN && !skip0 ? first0 / KT * KT : 0;
+  const int lo0_all = WIN ? r0_item[blockIdx.x * 2 + 1] - shift0 : 0;   // tiles below it: masked per row
+  const int r_start0 = r_start0_ + shift0, r_len0 = r_len0_ - shift0, kend0 = kend0_ - shift0;
   // R2 (suffix K/V reuse): every key of a suffix, the new rows' included, is read from the cache
   // as range 2 through per-row windows, so there is no range 1
   const int kend1 = (R2 || r_len1 <= 0) ? 0 : min(r_len1, q_off + q_len);
-  const int n0 = (kend0 + KT - 1) / KT;
+  const int n0 = skip0 ? 0 : (kend0 + KT - 1) / KT;
   // R2: range 2 = rows [r_start2, r_start2 + r_len2) of kv0 (a suffix's cached K/V), all visible,
   // walked between range 0 and range 1
   int r_start2 = 0, r_len2 = 0;
@@ -192,6 +211,9 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
       hi2[qg] = r2win[2 * qr + 1] - r_start2;
     }
   }
+  // WIN: the range-0 lower bounds of this lane's two query rows
+  const int lo0a = WIN ? r0_lo[q_start + min(rbase + fr, q_len - 1)] - shift0 : 0;
+  const int lo0b = WIN ? r0_lo[q_start + min(rbase + 16 + fr, q_len - 1)] - shift0 : 0;
   // the wave's first query row bounds every causal compare from below: a tile is fully visible to
   // the whole wave iff its last key is visible to that row (range 1 with several suffixes: masked)
   const int qi_min = q_off + rbase;
@@ -273,14 +295,15 @@ _Pragma("unroll") \
     } \
     FLS_ATTN_AFTER_QK \
     /* ---- visibility: wave-uniform fast path when every key of the tile is visible to every row */ \
-    const int vis_last = causal ? min(klen - 1, qi_min) : klen - 1; \
-    if (k0 + KT - 1 > vis_last || (r1 && multi) || r2) { \
+    /* (WIN: a causal range 0 compares against the query index behind the re-based range start) */ \
+    const int vis_last = causal ? min(klen - 1, qi_min - (WIN && !r1 ? shift0 : 0)) : klen - 1; \
+    if (k0 + KT - 1 > vis_last || (r1 && multi) || r2 || (WIN && !r1 && !r2 && k0 < lo0_all)) { \
       asm volatile("" ::: "memory");        /* keep this a branch (not per-score selects on every tile) */ \
 _Pragma("unroll") \
       for (int qg = 0; qg < NQ; ++qg) { \
         /* key k0 + 16tt + 4grp + r is visible iff lo_rel <= 16tt + r <= hi_rel */ \
-        const int hi_rel = (r2 ? min(klen, hi2[qg]) - 1 : (causal ? min(klen - 1, qi[qg]) : klen - 1)) - k0 - grp * 4; \
-        const int lo_rel = (r1 ? lo[qg] : (r2 ? lo2[qg] : 0)) - k0 - grp * 4; \
+        const int hi_rel = (r2 ? min(klen, hi2[qg]) - 1 : (causal ? min(klen - 1, qi[qg] - (WIN && !r1 ? shift0 : 0)) : klen - 1)) - k0 - grp * 4; \
+        const int lo_rel = (r1 ? lo[qg] : (r2 ? lo2[qg] : (WIN ? (qg ? lo0b : lo0a) : 0))) - k0 - grp * 4; \
 _Pragma("unroll") \
         for (int tt = 0; tt < 4; ++tt) \
 _Pragma("unroll") \
@@ -361,6 +384,16 @@ _Pragma("unroll") \
     if constexpr (!R2) {
       constexpr int NQ = 2;
       FLS_ATTN_TILE_MATH
+    } else if constexpr (WIN) {
+      // (as below, the tile's math expanded in place: through the lambda the windowed kernel kept
+      // its accumulators in scratch memory)
+      if (live_rows > 16) {
+        constexpr int NQ = 2;
+        FLS_ATTN_TILE_MATH
+      } else if (live_rows > 0) {
+        constexpr int NQ = 1;
+        FLS_ATTN_TILE_MATH
+      }
     } else {
       // a decode-like item holds a few new rows (one per suffix): the waves and 16-row groups past
       // q_len skip their MFMAs and softmax (wave-uniform), instead of padding every item to q_block
@@ -427,6 +460,7 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd_pers(const half_t*
                                                          int ld_qkv, int ld_out, float scale_log2,
                                                          const half_t* __restrict__ kv0, int ld_kv0, int n_items) {
   constexpr bool R2 = false;
+  constexpr bool WIN = false;               // windowed full passes take attn_fwd
   constexpr int NT_ = 64 * WPH * HPB;
   constexpr int NS = HD / 32;
   constexpr int NU = HD / 16;
@@ -484,6 +518,7 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd_pers(const half_t*
   half8 qf[2][NS];
   int qi[2], lo[2];
   const int lo2[2] = {0, 0}, hi2[2] = {0, 0};
+  constexpr int lo0_all = 0, lo0a = 0, lo0b = 0, shift0 = 0;
   auto load_q = [&](const UP& p) {
     const int h = p.hg * HPB + hw;
 #pragma unroll
@@ -653,12 +688,15 @@ __global__ __launch_bounds__(HD) void attn_split_combine(const float* __restrict
 //   * the softmax and O^T += V^T.P^T steps are attn_fwd's (deferred rescale, lane-local P^T).
 // SPL: blockIdx.z takes one of gridDim.z contiguous slices of the key tiles and writes fp32
 // partials in attn_split_combine's layout.
-template <int HD, bool SPL, int NB>
+// WIN: attn_fwd's range-0 window (r0_lo per row, r0_item per item).
+template <int HD, bool SPL, int NB, bool WIN = false>
 __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__ qkv, half_t* __restrict__ out,
                                                     const int* __restrict__ work, int nh, int nkv, int ld_qkv,
                                                     int ld_out, float scale_log2, const half_t* __restrict__ kv0,
                                                     int ld_kv0, const int* __restrict__ work2,
-                                                    const int* __restrict__ r2win, float* __restrict__ part) {
+                                                    const int* __restrict__ r2win, float* __restrict__ part,
+                                                    const int* __restrict__ r0_lo,
+                                                    const int* __restrict__ r0_item) {
   constexpr int NW = 4;                     // waves per block (16 packed rows each)
   // NB: tile ring depth (NB - 1 tiles in flight under the math of one)
   constexpr int NS = HD / 32;               // k-steps of QK^T
@@ -682,7 +720,13 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
   const int kend0 = r_len0 <= 0 ? 0 : (r_causal0 ? min(r_len0, q_off + q_len) : r_len0);
   const int r_start2 = work2[blockIdx.x * 2];
   const int r_len2 = max(work2[blockIdx.x * 2 + 1], 0);
-  const int n0 = (kend0 + KT - 1) / KT;
+  int t0s = 0, lo0_all = 0;                 // WIN: first range-0 tile walked, first key every row sees
+  if constexpr (WIN) {
+    const int first = min(max(r0_item[blockIdx.x * 2], 0), max(r_len0, 0));
+    lo0_all = r0_item[blockIdx.x * 2 + 1];
+    t0s = first < kend0 ? first / KT : (kend0 + KT - 1) / KT;
+  }
+  const int n0 = (kend0 + KT - 1) / KT - t0s;
   const int ntiles = n0 + (r_len2 + KT - 1) / KT;
   int t_lo = 0, t_hi = ntiles;
   if constexpr (SPL) {
@@ -698,7 +742,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
   const int drow = lane / CH, dpc = lane % CH;
   auto issue = [&](int t, int b) {
     const bool r2 = t >= n0;
-    const int k0 = (r2 ? t - n0 : t) * KT;
+    const int k0 = (r2 ? t - n0 : (WIN ? t + t0s : t)) * KT;
     const int klen = r2 ? r_len2 : kend0;
     const half_t* src = kv0 + (size_t)(r2 ? r_start2 : r_start0) * ld_kv0;
     char* Kd = smem + b * 2 * TB;
@@ -729,6 +773,8 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
     const int hi0 = r_causal0 ? min(kend0, q_off + r + 1) : kend0;     // range 0: keys [0, hi0)
     const int lo2 = r2win[2 * qr] - r_start2;                          // range 2: keys [lo2, hi2)
     const int hi2 = min(r2win[2 * qr + 1] - r_start2, r_len2);
+    int lo0_ = 0;                                                      // WIN: range 0: keys [lo0_, hi0)
+    if constexpr (WIN) lo0_ = r0_lo[qr];
     // (lo2_, hi2_ below: the same values, pinned before the DMAs)
     floatx4 o[NU];
 #pragma unroll
@@ -739,6 +785,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
     // so the compiler's own wait for them does not land behind the DMAs and drain the ring)
     int lo2_ = lo2, hi2_ = hi2;
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(lo2_), "+v"(hi2_)::"memory");
+    if constexpr (WIN) asm volatile("s_waitcnt vmcnt(0)" : "+v"(lo0_)::"memory");
 #pragma unroll
     for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(qf[s]));
 #pragma unroll
@@ -760,7 +807,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
       const char* Ks = smem + b * 2 * TB;
       const char* Vs = Ks + TB;
       const bool r2 = t >= n0;
-      const int k0 = (r2 ? t - n0 : t) * KT;
+      const int k0 = (r2 ? t - n0 : (WIN ? t + t0s : t)) * KT;
       // ---- S^T = K Q^T
       floatx4 sc[4];
 #pragma unroll
@@ -771,9 +818,9 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
           sc[tt] = mfma16x16x32(*(const half8*)(Ks + Lds<HD>::k_off(tt * 16 + fr, s * 4 + grp)), qf[s], sc[tt]);
       }
       // ---- visibility: range 0 tiles inside every row's keys take the unmasked path
-      if (r2 || r_causal0 || k0 + KT > kend0) {
+      if (r2 || r_causal0 || k0 + KT > kend0 || (WIN && k0 < lo0_all)) {
         asm volatile("" ::: "memory");
-        const int lo_rel = (r2 ? lo2_ : 0) - k0 - grp * 4;
+        const int lo_rel = (r2 ? lo2_ : (WIN ? lo0_ : 0)) - k0 - grp * 4;
         const int hi_rel = (r2 ? hi2_ : hi0) - k0 - grp * 4;             // exclusive
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
@@ -877,33 +924,33 @@ __global__ __launch_bounds__(256, 1) void attn_decode(const half_t* __restrict__
 // 46.3 vs 42.7 us per launch, HBM-resident caches (profiles/r5_gen/attn_decode_ring.log)
 constexpr int DECODE_RING = 3;
 
-template <int HD>
+template <int HD, bool WIN>
 int launch_decode(dim3 grid, int ns, hipStream_t st, const half_t* qkv, half_t* out, const int* work, int nh, int nkv,
                   int ld_qkv, int ld_out, float scale_log2, const half_t* kv0, int ld_kv0, const int* work2,
-                  const int* r2win, float* part) {
+                  const int* r2win, float* part, const int* r0_lo, const int* r0_item) {
   if (ns > 1) {
-    hipLaunchKernelGGL((attn_decode<HD, true, DECODE_RING>), dim3(grid.x, grid.y, ns), dim3(256), 0, st, qkv, out,
-                       work, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, part);
+    hipLaunchKernelGGL((attn_decode<HD, true, DECODE_RING, WIN>), dim3(grid.x, grid.y, ns), dim3(256), 0, st, qkv, out,
+                       work, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, part, r0_lo, r0_item);
     FLS_CHECK_LAUNCH();
     hipLaunchKernelGGL((attn_split_combine<HD>), dim3(grid.x, nh), dim3(HD), 0, st, part, out, work, nh, ld_out, ns);
   } else {
-    hipLaunchKernelGGL((attn_decode<HD, false, DECODE_RING>), grid, dim3(256), 0, st, qkv, out, work, nh, nkv, ld_qkv,
-                       ld_out, scale_log2, kv0, ld_kv0, work2, r2win, nullptr);
+    hipLaunchKernelGGL((attn_decode<HD, false, DECODE_RING, WIN>), grid, dim3(256), 0, st, qkv, out, work, nh, nkv,
+                       ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, nullptr, r0_lo, r0_item);
   }
   FLS_CHECK_LAUNCH();
   return 0;
 }
 
-template <int HD, int WPH, bool R2>
+template <int HD, int WPH, bool R2, bool WIN>
 int launch(int hpb, dim3 grid, hipStream_t st, const half_t* qkv, half_t* out, const int* work, const int* seg_lo,
            int nh, int nkv, int ld_qkv, int ld_out, float scale_log2, const half_t* kv0, int ld_kv0,
-           const int* work2, const int* r2win, float* part, int ns) {
+           const int* work2, const int* r2win, float* part, int ns, const int* r0_lo, const int* r0_item) {
   if constexpr (R2 && HD != 96) {
     if (ns > 1) {
       const dim3 g3(grid.x, grid.y, ns);
 #define FLS_ATTN_LAUNCH_SPL(HPB_)                                                                              \
-  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, true, true>), g3, dim3(64 * WPH * HPB_), 0, st, qkv, out, work, seg_lo, \
-                     nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, part)
+  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, true, true, WIN>), g3, dim3(64 * WPH * HPB_), 0, st, qkv, out, work, \
+                     seg_lo, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, part, r0_lo, r0_item)
       if constexpr (WPH == 1) {
         if (hpb == 8) FLS_ATTN_LAUNCH_SPL(8);
         else FLS_ATTN_LAUNCH_SPL(4);
@@ -923,8 +970,8 @@ int launch(int hpb, dim3 grid, hipStream_t st, const half_t* qkv, half_t* out, c
     }
   }
 #define FLS_ATTN_LAUNCH(HPB_)                                                                                  \
-  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, R2>), grid, dim3(64 * WPH * HPB_), 0, st, qkv, out, work, seg_lo, nh, \
-                     nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, nullptr)
+  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, R2, false, WIN>), grid, dim3(64 * WPH * HPB_), 0, st, qkv, out, work, \
+                     seg_lo, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, nullptr, r0_lo, r0_item)
   if constexpr (HD == 96) {
     FLS_ATTN_LAUNCH(1);                     // 12 chunks per row: one head per block divides the tile
   } else if constexpr (WPH == 1) {          // 4 or 8 heads (dispatch)
@@ -1013,11 +1060,11 @@ extern "C" int fls_attention_set_split(int ns) {
 }
 
 namespace {
-template <bool R2>
+template <bool R2, bool WIN>
 int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_heads, int n_kv_heads, int head_dim,
              int ld_qkv, int ld_out, float scale, const void* kv0, int ld_kv0, const int* seg_lo, int q_block,
              const int* work2, const int* r2win, void* ws, unsigned long long ws_bytes, int n_rows,
-             fls_stream_t s) {
+             fls_stream_t s, const int* r0_lo, const int* r0_item) {
   if (n_q_heads % n_kv_heads) return -2;
   if (head_dim != 64 && head_dim != 96 && head_dim != 128) return -3;
   // q_block 32 (one wave per head): range-2 items of at most 32 rows (generation steps);
@@ -1041,10 +1088,11 @@ int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_h
       auto q = (const half_t*)qkv;
       auto o = (half_t*)out;
       auto k0 = (const half_t*)kv0;
-      return head_dim == 128 ? launch_decode<128>(grid, ns, st, q, o, work, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                                  scale_log2, k0, ld_kv0, work2, r2win, (float*)ws)
-                             : launch_decode<64>(grid, ns, st, q, o, work, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                                 scale_log2, k0, ld_kv0, work2, r2win, (float*)ws);
+      return head_dim == 128
+                 ? launch_decode<128, WIN>(grid, ns, st, q, o, work, n_q_heads, n_kv_heads, ld_qkv, ld_out, scale_log2,
+                                           k0, ld_kv0, work2, r2win, (float*)ws, r0_lo, r0_item)
+                 : launch_decode<64, WIN>(grid, ns, st, q, o, work, n_q_heads, n_kv_heads, ld_qkv, ld_out, scale_log2,
+                                          k0, ld_kv0, work2, r2win, (float*)ws, r0_lo, r0_item);
     }
   }
   if (q_block == 8) q_block = 32;           // hd 96 (or the non-range-2 kernel): the per-head layout
@@ -1076,7 +1124,7 @@ int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_h
   auto q = (const half_t*)qkv;
   auto o = (half_t*)out;
   auto k0 = (const half_t*)kv0;
-  if constexpr (!R2) {
+  if constexpr (!R2 && !WIN) {              // (a windowed full pass: one block per item x head group)
     if (g_pers && head_dim != 96 && q_block != 32)
       return q_block == 64 ? (head_dim == 128 ? launch_pers<128, 2>(hpb, n_items, st, q, o, work, seg_lo, n_q_heads,
                                                                     n_kv_heads, ld_qkv, ld_out, scale_log2, k0, ld_kv0)
@@ -1089,25 +1137,25 @@ int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_h
   }
   if constexpr (R2) {
     if (q_block == 32)                      // head_dim 64 / 128 here (96 fell back above)
-      return head_dim == 128 ? launch<128, 1, true>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
-                                                    ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns)
-                             : launch<64, 1, true>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
-                                                   ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns);
+      return head_dim == 128 ? launch<128, 1, true, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
+                                                    ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
+                             : launch<64, 1, true, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
+                                                   ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
   }
   if (head_dim == 96)
-    return q_block == 64 ? launch<96, 2, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns)
-                         : launch<96, 4, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns);
+    return q_block == 64 ? launch<96, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
+                         : launch<96, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
   if (q_block == 64)
-    return head_dim == 128 ? launch<128, 2, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                            scale_log2, k0, ld_kv0, work2, r2win, part, ns)
-                           : launch<64, 2, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                           scale_log2, k0, ld_kv0, work2, r2win, part, ns);
-  return head_dim == 128 ? launch<128, 4, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                          scale_log2, k0, ld_kv0, work2, r2win, part, ns)
-                         : launch<64, 4, R2>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns);
+    return head_dim == 128 ? launch<128, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                            scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
+                           : launch<64, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                           scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
+  return head_dim == 128 ? launch<128, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                          scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
+                         : launch<64, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
 }
 }  // namespace
 
@@ -1117,8 +1165,29 @@ extern "C" int fls_attention(const void* qkv, void* out, const int* work, int n_
                              void* ws, unsigned long long ws_bytes, int n_rows, fls_stream_t s) {
   if (n_items <= 0) return 0;
   if (work2 && (!kv0 || !r2win)) return -6;   // range 2 indexes the K/V cache, per-row windows
-  return work2 ? dispatch<true>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale, kv0,
-                                ld_kv0, seg_lo, q_block, work2, r2win, ws, ws_bytes, n_rows, s)
-               : dispatch<false>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale, kv0,
-                                 ld_kv0, seg_lo, q_block, nullptr, nullptr, nullptr, 0, 0, s);
+  return work2 ? dispatch<true, false>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
+                                       kv0, ld_kv0, seg_lo, q_block, work2, r2win, ws, ws_bytes, n_rows, s, nullptr,
+                                       nullptr)
+               : dispatch<false, false>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
+                                        kv0, ld_kv0, seg_lo, q_block, nullptr, nullptr, nullptr, 0, 0, s, nullptr,
+                                        nullptr);
+}
+
+// Sliding-window form: fls_attention plus r0_lo ([rows] int32: the first range-0 key each row sees,
+// relative to the range start, in [0, r0_len]) and r0_item ([n_items, 2] int32: min and max of r0_lo
+// over each item's rows).  seg_lo and r2win carry the window for ranges 1 and 2 (runtime/batch.py).
+extern "C" int fls_attention_window(const void* qkv, void* out, const int* work, int n_items, int n_q_heads,
+                                    int n_kv_heads, int head_dim, int ld_qkv, int ld_out, float scale,
+                                    const void* kv0, int ld_kv0, const int* seg_lo, int q_block, const int* work2,
+                                    const int* r2win, void* ws, unsigned long long ws_bytes, int n_rows,
+                                    const int* r0_lo, const int* r0_item, fls_stream_t s) {
+  if (n_items <= 0) return 0;
+  if (work2 && (!kv0 || !r2win)) return -6;
+  if (!r0_lo || !r0_item) return -7;          // the window's per-row and per-item range-0 bounds
+  return work2 ? dispatch<true, true>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
+                                      kv0, ld_kv0, seg_lo, q_block, work2, r2win, ws, ws_bytes, n_rows, s, r0_lo,
+                                      r0_item)
+               : dispatch<false, true>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
+                                       kv0, ld_kv0, seg_lo, q_block, nullptr, nullptr, nullptr, 0, 0, s, r0_lo,
+                                       r0_item);
 }

@@ -232,6 +232,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          suffix_kv_cache=skv, exact_reuse=getattr(args, "exact_reuse", True),
                          pipeline_stages=getattr(args, "pipeline_stages", "round_robin"),
                          rx_window=getattr(args, "rx_window", 2),
+                         sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          max_vram_gb=getattr(args, "max_vram_gb", None))
 
 

@@ -79,7 +79,10 @@ class ShardedRunner:
                  prefix_kv_cache: bool = False, prefix_cache_entries: int = 8, suffix_kv_cache: bool = False,
                  prune_last_layer: bool = True, pipeline_stages: str = "round_robin",
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
-                 exact_reuse: bool = True):
+                 exact_reuse: bool = True, sliding_window_mode: str = "error"):
+        if sliding_window_mode not in ("error", "apply"):
+            raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
+        self.sliding_window_mode = sliding_window_mode
         self.cfg = cfg
         self.src = source
         # layers read from their files every pass (no host-resident copy): host RAM is the limit
@@ -414,6 +417,23 @@ class ShardedRunner:
                 ctx.row_exact = self.prev
         return _RowExact()
 
+    def _call_window(self, tps) -> int:
+        """The sliding window this call packs with: 0 while every sequence fits
+        ``cfg.sliding_window`` (windowed attention then equals full attention: query i sees keys
+        i - sw + 1 .. i, and the call takes the unwindowed path unchanged); for a longer one the
+        window itself under ``sliding_window_mode="apply"``, an error under ``"error"``."""
+        sw = self.cfg.sliding_window
+        if not sw:
+            return 0
+        longest = max((len(tp.prefix) + max((len(s) for s in tp.suffixes), default=0) for tp in tps),
+                      default=0)
+        if longest <= sw:
+            return 0
+        if self.sliding_window_mode != "apply":
+            raise ValueError(f"a prompt spans {longest} tokens > sliding_window={sw}: "
+                             "sliding-window attention is not implemented")
+        return int(sw)
+
     def run_tokenized(self, tps: Sequence[TokenizedPrompt]) -> List[Optional[np.ndarray]]:
         t_start = time.perf_counter()
         spec, self._spec = self._spec, None
@@ -422,15 +442,7 @@ class ShardedRunner:
                 return self._finish_spec(spec, tps, t_start)
             self._drop_spec(spec)
         n = len(tps)
-        sw = self.cfg.sliding_window
-        if sw:
-            # windowed attention equals full attention while every sequence fits the window
-            # (HF: query i sees keys i - sw + 1 .. i); longer ones would need the band mask
-            longest = max((len(tp.prefix) + max((len(s) for s in tp.suffixes), default=0) for tp in tps),
-                          default=0)
-            if longest > sw:
-                raise ValueError(f"a prompt spans {longest} tokens > sliding_window={sw}: "
-                                 "sliding-window attention is not implemented")
+        window = self._call_window(tps)
         entry, cached = self._prefix_entry(tps)
         if self._vram_cap:
             self._plan_call(tps, cached)
@@ -447,7 +459,7 @@ class ShardedRunner:
                                 kv_cached=cached, q_block=self.q_block,
                                 suffix_rows=[sfx_rows[i] for i in g] if sfx_rows is not None else None,
                                 suffix_keep=[sfx_keep[i] for i in g] if sfx_keep is not None else None,
-                                single_suffix_items=self.row_exact)
+                                single_suffix_items=self.row_exact, window=window)
                    for g in groups]
         t_pack = time.perf_counter() - t_start
         if self.hip_graphs:
@@ -1121,7 +1133,8 @@ class ShardedRunner:
                 keep.append([len(s) - 1 for s in tp.suffixes])
             sb = [pack_prompts([spec_tps[i] for i in g], g, self.prefix_attention,
                                prefix_offsets=[entry.offsets[i] for i in g], kv_cached=True, q_block=self.q_block,
-                               suffix_rows=[rows[i] for i in g], suffix_keep=[keep[i] for i in g]) for g in groups]
+                               suffix_rows=[rows[i] for i in g], suffix_keep=[keep[i] for i in g],
+                               window=self._call_window(spec_tps)) for g in groups]
             if not self._decode_graphable(sb, True) or any(x.num_tokens != b.n_scored for x, b in zip(sb, batches)):
                 return None
             graphs = self._decode_graphs

@@ -433,6 +433,9 @@ def _attention_whole(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tens
     if work_items and "work2" in meta:       # suffix K/V reuse: range 2 = the suffixes' kept rows
         kw["work2"] = meta["work2_last"] if prune else meta["work2"]
         kw["r2win"] = meta["r2win"]
+    if work_items and "r0_lo" in meta:       # sliding window: per-row / per-item range-0 bounds
+        kw["r0_lo"] = meta["r0_lo"]
+        kw["r0_item"] = meta["r0_item_last"] if prune else meta["r0_item"]
     qb = batch.r2_q_block if "work2" in kw else batch.q_block     # (work_last items: one row each)
     a = ops.attention(qkv, attn_arg, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim,
                       kv0=kv0 if batch.kv_cached else None, q_block=qb, out=qkv[:, :cfg.q_size],
@@ -478,6 +481,9 @@ def _attention_grouped(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Te
         else:
             arg = g["work"] if work_items else g["segments"]
         kw = {"seg_lo": g["seg_lo"]} if work_items else {}
+        if work_items and "r0_lo" in g:      # sliding window
+            kw["r0_lo"] = g["r0_lo"]
+            kw["r0_item"] = g["r0_item_last"] if prune else g["r0_item"]
         a = ops.attention(qkv, arg, nq, nkv, hd, q_block=batch.q_block, out=qkv[:, :cfg.q_size],
                           scale=cfg.attn_scale, **kw)
         if prune:

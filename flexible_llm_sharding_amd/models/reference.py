@@ -100,7 +100,10 @@ def _moe(h, sd, p, cfg):
 def reference_scores(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence,
                      prefix_attention: str = "bidirectional", max_len: int = 4096,
                      cos=None, sin=None) -> List[np.ndarray]:
-    """list of [n_s, 1, V] float32 probabilities, one per prompt."""
+    """list of [n_s, 1, V] float32 probabilities, one per prompt.  ``cfg.sliding_window`` W: a key at
+    position j is visible to a query at position i only if i - j < W (W keys, the row's own
+    included: the rule of transformers 5.x); the window only cuts off the past, so bidirectional
+    prefix queries still see every later prefix key."""
     from .llama import rope_tables
     from ..utils.synthetic import split_projections
     sd = split_projections(cfg, sd)          # Phi-3 fused qkv_proj / gate_up_proj -> split names
@@ -122,6 +125,11 @@ def reference_scores(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts
         if prefix_attention == "causal":
             pmask = torch.full((Lp, Lp), neg).triu(1)[None, None]
         full = torch.full((Lp + Ls, Lp + Ls), neg).triu(1)
+        if cfg.sliding_window:
+            W = int(cfg.sliding_window)
+            full = torch.minimum(full, torch.full((Lp + Ls, Lp + Ls), neg).tril(-W))
+            band = torch.full((Lp, Lp), neg).tril(-W)[None, None]
+            pmask = band if pmask is None else torch.minimum(pmask, band)
         smask = full[-Ls:, -(Lp + Ls):][None, None].expand(ns, 1, Ls, Lp + Ls)   # utils.py:276
         for i in range(cfg.num_hidden_layers):
             p = f"model.layers.{i}"

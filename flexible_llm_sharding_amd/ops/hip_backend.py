@@ -413,12 +413,15 @@ class HipOps:
 
     # ----------------------------------------------------------- attention
     def attention(self, qkv, work, n_q_heads, n_kv_heads, head_dim, kv0=None, q_block: int = 64, out=None,
-                  seg_lo=None, work2=None, r2win=None, scale=None):
+                  seg_lo=None, work2=None, r2win=None, scale=None, r0_lo=None, r0_item=None):
         """kv0 ([P, 2 * n_kv * hd], K then V): range 0 of every work item reads these rows (prefix cache).
         seg_lo ([T] int32, first row of each row's suffix): work items may span several suffixes.
         work2 ([n_items, 2] int32: r2_start, r2_len) + r2win ([T, 2] int32: kv0 rows [lo, hi) per row):
         range 2 = the kv0 rows of the item's suffixes cached by an earlier call (suffix K/V reuse),
-        walked between the prefix and the new rows, each row seeing its own suffix's window."""
+        walked between the prefix and the new rows, each row seeing its own suffix's window.
+        r0_lo ([T] int32: first range-0 key each row sees, relative to the range start) + r0_item
+        ([n_items, 2] int32: its min and max over each item's rows): sliding-window attention
+        (PackedBatch.r0_lo / r0_item; seg_lo and r2win then carry the window of ranges 1 and 2)."""
         _f16(qkv, "qkv")
         if work.dtype != torch.int32 or not work.is_cuda:
             raise TypeError("work items must be an int32 CUDA tensor")
@@ -435,6 +438,13 @@ class HipOps:
                                   or tuple(work2.shape) != (work.shape[0], 2) or r2win is None
                                   or r2win.dtype != torch.int32 or r2win.shape[0] < T):
             raise TypeError("work2 must be int32 CUDA [n_items, 2] with r2win [T, 2] and kv0")
+        if (r0_lo is None) != (r0_item is None):
+            raise TypeError("r0_lo and r0_item (sliding window) come together")
+        if r0_lo is not None and (r0_lo.dtype != torch.int32 or not r0_lo.is_cuda or r0_lo.dim() != 1
+                                  or r0_lo.shape[0] < T or not r0_lo.is_contiguous()
+                                  or r0_item.dtype != torch.int32 or not r0_item.is_cuda
+                                  or tuple(r0_item.shape) != (work.shape[0], 2) or not r0_item.is_contiguous()):
+            raise TypeError("r0_lo must be int32 CUDA [T] with r0_item int32 CUDA [n_items, 2]")
         if out is None:
             out = torch.empty(T, n_q_heads * head_dim, dtype=torch.float16, device=qkv.device)
         # the range-2 (decode-like) kernel splits its key tiles over blocks when the grid is small;
@@ -442,16 +452,19 @@ class HipOps:
         # (row-exact calls: no split, whose merge would round differently from the unsplit kernel)
         ws = self._splitk_ws(qkv.device, 0, 0) if work2 is not None and not getattr(self._tl, "row_exact", False) \
             else None
-        rc = self.k.fls_attention(qkv.data_ptr(), out.data_ptr(), work.data_ptr(), work.shape[0],
-                                  n_q_heads, n_kv_heads, head_dim, qkv.stride(0), out.stride(0),
-                                  head_dim ** -0.5 if scale is None else float(scale),
-                                  kv0.data_ptr() if kv0 is not None else None,
-                                  kv0.stride(0) if kv0 is not None else 0,
-                                  seg_lo.data_ptr() if seg_lo is not None else None, q_block,
-                                  work2.data_ptr() if work2 is not None else None,
-                                  r2win.data_ptr() if work2 is not None else None,
-                                  ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                  T, _stream())
+        args = (qkv.data_ptr(), out.data_ptr(), work.data_ptr(), work.shape[0],
+                n_q_heads, n_kv_heads, head_dim, qkv.stride(0), out.stride(0),
+                head_dim ** -0.5 if scale is None else float(scale),
+                kv0.data_ptr() if kv0 is not None else None,
+                kv0.stride(0) if kv0 is not None else 0,
+                seg_lo.data_ptr() if seg_lo is not None else None, q_block,
+                work2.data_ptr() if work2 is not None else None,
+                r2win.data_ptr() if work2 is not None else None,
+                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, T)
+        if r0_lo is not None:
+            rc = self.k.fls_attention_window(*args, r0_lo.data_ptr(), r0_item.data_ptr(), _stream())
+        else:
+            rc = self.k.fls_attention(*args, _stream())
         _chk(rc, "fls_attention")
         return out
 

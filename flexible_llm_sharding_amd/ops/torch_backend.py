@@ -181,6 +181,18 @@ class TorchOps:
                 if causal:
                     m = kj[None, :] <= qi[:, None]
                 masks.append(m)
+            W = getattr(sg, "window", 0)
+            if W:
+                # sliding window over model positions: prefix token p at p; token s of a suffix at
+                # r0_len + s, its kept rows (range 2) first.  Only the past is cut off.
+                r2l = getattr(sg, "r2_len", 0)
+                qpos = qi + (sg.r0_len + r2l if sg.r1_len else 0)
+                kpos = [torch.arange(sg.r0_len, device=dev)]
+                if r2l:
+                    kpos.append(sg.r0_len + torch.arange(r2l, device=dev))
+                if sg.r1_len:
+                    kpos.append(sg.r0_len + r2l + torch.arange(sg.r1_len, device=dev))
+                masks = [torch.cat(masks, 1) & (qpos[:, None] - torch.cat(kpos)[None, :] < W)]
             k = self._c(torch.cat(ks_, 0)).repeat_interleave(rep, dim=1)        # [k, nh, d]
             v = self._c(torch.cat(vs_, 0)).repeat_interleave(rep, dim=1)
             mask = torch.cat(masks, 1)                                          # [q, k]

@@ -359,6 +359,7 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                                           else getattr(args, "prefix_kv_cache", False) is True),
                          prefix_cache_entries=getattr(args, "prefix_cache_entries", 8),
                          suffix_kv_cache=_suffix_kv(args, comm), exact_reuse=getattr(args, "exact_reuse", True),
+                         sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          max_vram_gb=getattr(args, "max_vram_gb", None))
 
 

@@ -53,6 +53,9 @@ class Segment:
     q_off: int = 0       # index of the first query inside its segment (causal compare)
     r2_start: int = 0    # suffix K/V reuse: rows of the K/V cache holding this suffix's earlier
     r2_len: int = 0      # tokens (all visible), between the prefix (r0) and the new rows (r1)
+    window: int = 0      # sliding window W > 0: a key at model position j is visible to a query at
+                         # position i only if i - j < W (prefix token p: position p; token s of a
+                         # suffix: r0_len + s, kept rows included); the window only cuts off the past
 
 
 # range-2 (generation-step) attention items of <= 8 rows: the packed-GQA decode kernel
@@ -87,6 +90,13 @@ class PackedBatch:
     work2_last: Optional[np.ndarray] = None     # [S_total, 2] the same for ``work_last``
     sfx_src: Optional[np.ndarray] = None        # capture: packed rows of suffix tokens ...
     sfx_dst: Optional[np.ndarray] = None        # ... and their rows in the K/V cache
+    window: int = 0                             # sliding window the arrays below (and seg_lo / r2win) apply
+    r0_lo: Optional[np.ndarray] = None          # [T] first range-0 key each row sees, relative to the
+                                                # range start, in [0, r0_len] (r0_len: no prefix key)
+    r0_item: Optional[np.ndarray] = None        # [n_items, 2] min / max of r0_lo over the item's rows: the
+                                                # kernel walks range 0 from the 64-key tile of the min,
+                                                # and masks by r0_lo the tiles that start below the max
+    r0_item_last: Optional[np.ndarray] = None   # [S_total, 2] the same for ``work_last``
     _dev: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -141,7 +151,9 @@ class PackedBatch:
             r0, r1 = int(self.prompt_rows[g[0], 0]), int(self.prompt_rows[g[-1], 1])
             w0, w1 = int(self.prompt_items[g[0], 0]), int(self.prompt_items[g[-1], 1])
             s0, s1 = int(self.prompt_scored[g[0], 0]), int(self.prompt_scored[g[-1], 1])
-            out.append({"r0": r0, "r1": r1, "s0": s0, "s1": s1,
+            win = {} if self.r0_lo is None else {      # relative to each range start: nothing to rebase
+                "r0_lo": self.r0_lo[r0:r1], "r0_item": self.r0_item[w0:w1], "r0_item_last": self.r0_item_last[s0:s1]}
+            out.append({"r0": r0, "r1": r1, "s0": s0, "s1": s1, **win,
                         "work": self._rebase(self.work[w0:w1], r0),
                         "work_last": self._rebase(self.work_last[s0:s1], r0),
                         "seg_lo": (self.seg_lo[r0:r1] - r0).astype(np.int32),
@@ -184,7 +196,8 @@ class PackedBatch:
         m = {"ids": self.ids, "positions": self.positions, "work": self.work, "seg_lo": self.seg_lo,
              "last_idx": self.last_idx, "last_pos": self.positions[self.last_idx].astype(np.int32),
              "work_last": self.work_last}
-        for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win"):
+        for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win",
+                     "r0_lo", "r0_item", "r0_item_last"):
             v = getattr(self, name)
             if v is not None:
                 m[name] = v
@@ -206,7 +219,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                  kv_cached: bool = False, q_block: int = Q_BLOCK,
                  suffix_rows: Optional[Sequence[Sequence[int]]] = None,
                  suffix_keep: Optional[Sequence[Sequence[int]]] = None,
-                 single_suffix_items: bool = False) -> PackedBatch:
+                 single_suffix_items: bool = False, window: int = 0) -> PackedBatch:
     """Pack prompts into one token matrix + attention work items.
 
     ``prefix_offsets`` (rows of each prompt's prefix in a PrefixEntry) turns on
@@ -224,7 +237,18 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     at a multiple of 64 tokens from its suffix's first token, as the range-2 tiles of a reused step
     do over 64-row-aligned cache regions (generation with the prefix K/V cache: each row's attention
     then takes the same tiles, whichever step computes it; engine ``row_exact``).
+
+    ``window`` (W > 0): sliding-window attention.  A key at model position j stays visible to a
+    query at position i only if i - j < W (W keys, the row's own included).  The window reaches the
+    kernel as per-row lower bounds: ``seg_lo`` (range 1) and ``r2win[:, 0]`` (range 2) are raised to
+    the first key inside the window, ``r0_lo`` is the same bound for range 0, and ``r0_item`` /
+    ``work2`` start each item's walk at the 64-key tile of its rows' smallest bound (tiles stay at
+    multiples of 64 keys from the unwindowed range start, so a row meets the same tiles in every
+    step that computes it).
     """
+    if window < 0:
+        raise ValueError(f"window={window}")
+    W = int(window)
     if prefix_attention not in ("bidirectional", "causal"):
         raise ValueError(prefix_attention)
     if kv_cached and prefix_offsets is None:
@@ -238,6 +262,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     if suffix_keep is not None and any(r < 0 for rows in suffix_rows for r in rows):
         raise ValueError("suffix K/V reuse needs a cache region for every suffix")
     work, work2, r2win, lwork, lwork2 = [], [], [], [], []
+    r0_lo, r0_item, r0_item_last = [], [], []
     src, dst, sfx_src, sfx_dst = [], [], [], []
     p_rows, p_items, p_scored = [], [], []
     t = 0
@@ -252,16 +277,21 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             p0 = t
             ids.append(np.asarray(tp.prefix, dtype=np.int32))
             pos.append(np.arange(Lp, dtype=np.int32))
-            segs.append(Segment(p0, Lp, p0, Lp, pcausal, 0, 0))
+            segs.append(Segment(p0, Lp, p0, Lp, pcausal, 0, 0, window=W))
             seg_lo.append(np.full(Lp, p0, dtype=np.int32))
             work.extend(_items(segs[-1], q_block))
             work2.extend([(0, 0)] * (len(work) - len(work2)))
+            if W:
+                plo = np.maximum(np.arange(Lp, dtype=np.int32) - (W - 1), 0)
+                r0_lo.append(plo)
+                r0_item.extend((int(plo[o]), int(plo[min(o + q_block, Lp) - 1])) for o in range(0, Lp, q_block))
             if prefix_offsets is not None:
                 src.append(np.arange(t, t + Lp, dtype=np.int32))
                 dst.append(np.arange(prefix_offsets[j], prefix_offsets[j] + Lp, dtype=np.int32))
             t += Lp
-        sfx0 = t
+        sfx0, lo_parts0 = t, len(r0_lo)
         sfx_lo = []                    # seg_lo of this prompt's suffix rows (row - sfx0)
+        sfx_of = []                    # index of the suffix holding each of them
         keep = suffix_keep[j] if suffix_keep is not None else None
         for si, s in enumerate(tp.suffixes):
             c = keep[si] if keep is not None else 0
@@ -270,17 +300,26 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             s0 = t
             ids.append(np.asarray(s[c:], dtype=np.int32))
             pos.append(np.arange(Lp + c, Lp + c + n, dtype=np.int32))
-            seg_lo.append(np.full(n, s0, dtype=np.int32))
+            # range 1 (row s0 + i = token c + i of the suffix): keys from row - W + 1 on
+            seg_lo.append(np.maximum(np.arange(s0, s0 + n, dtype=np.int32) - (W - 1), s0) if W
+                          else np.full(n, s0, dtype=np.int32))
             sfx_lo.extend([s0] * n)
+            sfx_of.extend([si] * n)
+            if W:
+                r0_lo.append(np.clip(np.arange(Lp + c, Lp + c + n, dtype=np.int32) - (W - 1), 0, Lp))
+                r0_item_last.append((int(r0_lo[-1][-1]),) * 2)
             r2s, r2l = (c0_row, c) if c else (0, 0)
-            segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l))
+            segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l, window=W))
             last.append(s0 + n - 1)
             # the scored row alone, for a last decoder layer that computes only scored rows
-            lsegs.append(Segment(s0 + n - 1, 1, p0, Lp, 0, s0, n, q_off=n - 1, r2_start=r2s, r2_len=r2l))
+            lsegs.append(Segment(s0 + n - 1, 1, p0, Lp, 0, s0, n, q_off=n - 1, r2_start=r2s, r2_len=r2l,
+                                 window=W))
             if keep is not None:
                 # its work item (HIP): the whole suffix from the cache through the row's window
                 lwork.append((s0 + n - 1, 1, 0, p0, Lp, 0, 0, 0))
-                lwork2.append((c0_row, c + n))
+                # (windowed: from the 64-row tile of the scored row's first visible cache row)
+                wl = max(c + n - W, 0) // 64 * 64 if W else 0
+                lwork2.append((c0_row + wl, c + n - wl))
             if c0_row >= 0:
                 sfx_src.append(np.arange(s0, s0 + n, dtype=np.int32))
                 sfx_dst.append(np.arange(c0_row + c, c0_row + c + n, dtype=np.int32))
@@ -289,12 +328,14 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                 # after the kept ones: new row i sees cache rows [c0_row, c0_row + c + i] (its own
                 # key included: causal by window), so the kernel needs no range 1 at all.  (With
                 # keep every packed row is a suffix row: the prefixes come from the cache.)
-                r2win.extend([(c0_row, c0_row + c + i + 1) for i in range(n)])
+                # (windowed: from cache row c0_row + c + i - W + 1 on)
+                r2win.extend([(c0_row + (max(c + i + 1 - W, 0) if W else 0), c0_row + c + i + 1) for i in range(n)])
             t += n
         # the prompt's suffix rows [sfx0, t) in q_block chunks; range 1 of a chunk starts at the
         # suffix holding its first row.  Suffix K/V reuse: range 2 of every chunk spans the kept
         # rows of all the prompt's suffixes, each row seeing only its own suffix's window (r2win)
         chunks = [(c0, min(c0 + q_block, t)) for c0 in range(sfx0, t, q_block)]
+        sfx_r0 = np.concatenate(r0_lo[lo_parts0:]) if W and t > sfx0 else None   # r0_lo of rows [sfx0, t)
         if single_suffix_items and keep is None:
             chunks = [(s0 + o, min(s0 + o + q_block, s0 + n)) for sg in segs if sg.r1_len and sg.q_start >= sfx0
                       for s0, n in [(sg.q_start, sg.q_len)] for o in range(0, n, q_block)]
@@ -302,12 +343,20 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             if keep is not None:
                 w = r2win[c0:c1]
                 lo, hi = min(a for a, _ in w), max(b for _, b in w)
+                if W:
+                    # the walk starts at a multiple of 64 rows from where it starts without the
+                    # window (the first cache row of the chunk's suffixes): the same tile grid
+                    base = min(suffix_rows[j][si] for si in sfx_of[c0 - sfx0:c1 - sfx0])
+                    lo = base + (lo - base) // 64 * 64
                 work.append((c0, c1 - c0, 0, p0, Lp, 0, 0, 0))
                 work2.append((lo, hi - lo))
             else:
                 r1 = sfx_lo[c0 - sfx0]
                 work.append((c0, c1 - c0, c0 - r1, p0, Lp, 0, r1, c1 - r1))
                 work2.append((0, 0))
+            if W:
+                rl = sfx_r0[c0 - sfx0:c1 - sfx0]
+                r0_item.append((int(rl.min()), int(rl.max())))
         max_pos = max(max_pos, Lp + max([len(s) for s in tp.suffixes] or [0]))
         p_rows.append((row0, t))
         p_items.append((item0, len(work)))
@@ -336,7 +385,11 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         r2win=np.asarray(r2win, dtype=np.int32).reshape(-1, 2) if reuse else None,
         work2_last=np.asarray(lwork2, dtype=np.int32).reshape(-1, 2) if reuse else None,
         sfx_src=cat(sfx_src) if sfx_src else None,
-        sfx_dst=cat(sfx_dst) if sfx_dst else None)
+        sfx_dst=cat(sfx_dst) if sfx_dst else None,
+        window=W,
+        r0_lo=cat(r0_lo) if W else None,
+        r0_item=np.asarray(r0_item, dtype=np.int32).reshape(-1, 2) if W else None,
+        r0_item_last=np.asarray(r0_item_last, dtype=np.int32).reshape(-1, 2) if W else None)
 
 
 def _items(sg: Segment, q_block: int = Q_BLOCK) -> List[tuple]:
@@ -353,7 +406,8 @@ def _work_items(segs: Sequence[Segment], q_block: int = Q_BLOCK) -> np.ndarray:
 
 
 def visible_keys(work: np.ndarray, seg_lo: Optional[np.ndarray], row: int,
-                 work2: Optional[np.ndarray] = None, r2win: Optional[np.ndarray] = None) -> List[tuple]:
+                 work2: Optional[np.ndarray] = None, r2win: Optional[np.ndarray] = None,
+                 r0_lo: Optional[np.ndarray] = None) -> List[tuple]:
     """(range, first key row, last key row) visible to packed query ``row`` under the work items:
     the semantics of the attention kernel (csrc/kernels/attention.hip), for host-side tests."""
     for it, (q_start, q_len, q_off, r0s, r0l, r0c, r1s, r1l) in enumerate(work.tolist()):
@@ -361,7 +415,10 @@ def visible_keys(work: np.ndarray, seg_lo: Optional[np.ndarray], row: int,
             qi = q_off + row - q_start
             out = []
             if r0l > 0:
-                out.append((0, r0s, r0s + (min(r0l - 1, qi) if r0c else r0l - 1)))
+                hi = min(r0l - 1, qi) if r0c else r0l - 1
+                lo = int(r0_lo[row]) if r0_lo is not None else 0    # windowed: the row's own bound
+                if hi >= lo:
+                    out.append((0, r0s + lo, r0s + hi))
             if work2 is not None and work2[it, 1] > 0:
                 lo, hi = int(work2[it, 0]), int(work2[it, 0] + work2[it, 1])
                 if r2win is not None:

@@ -45,13 +45,15 @@ def _ceil(n: int, m: int) -> int:
     return max(m, (n + m - 1) // m * m)
 
 
-def bucket_key(batch: PackedBatch) -> Tuple[int, int, int]:
-    return (_ceil(batch.num_tokens, TOKEN_BUCKET), _ceil(batch.work.shape[0], WORK_BUCKET),
-            _ceil(batch.n_scored, SCORE_BUCKET))
+def bucket_key(batch: PackedBatch) -> tuple:
+    key = (_ceil(batch.num_tokens, TOKEN_BUCKET), _ceil(batch.work.shape[0], WORK_BUCKET),
+           _ceil(batch.n_scored, SCORE_BUCKET))
+    # a windowed batch replays a graph of its own (other kernels, three more static inputs)
+    return key + (("window",) if batch.r0_lo is not None else ())
 
 
 def padded_meta(batch: PackedBatch, key) -> Dict[str, np.ndarray]:
-    T, W, S = key
+    T, W, S = key[:3]
     ids = np.zeros(T, np.int32)
     ids[:batch.num_tokens] = batch.ids
     pos = np.zeros(T, np.int32)
@@ -65,8 +67,16 @@ def padded_meta(batch: PackedBatch, key) -> Dict[str, np.ndarray]:
     last_pos = pos[last]                                   # positions of the scored rows
     wl = np.zeros((S, WORK_ITEM_FIELDS), np.int32)        # padding items: q_len 0
     wl[:batch.work_last.shape[0]] = batch.work_last
-    return {"ids": ids, "positions": pos, "work": work, "seg_lo": seg_lo, "last_idx": last, "last_pos": last_pos,
+    meta = {"ids": ids, "positions": pos, "work": work, "seg_lo": seg_lo, "last_idx": last, "last_pos": last_pos,
             "work_last": wl}
+    if batch.r0_lo is not None:                            # sliding window (padding items never read theirs)
+        meta["r0_lo"] = np.zeros(T, np.int32)
+        meta["r0_lo"][:batch.num_tokens] = batch.r0_lo
+        meta["r0_item"] = np.zeros((W, 2), np.int32)
+        meta["r0_item"][:batch.r0_item.shape[0]] = batch.r0_item
+        meta["r0_item_last"] = np.zeros((S, 2), np.int32)
+        meta["r0_item_last"][:batch.r0_item_last.shape[0]] = batch.r0_item_last
+    return meta
 
 
 class _Graph:

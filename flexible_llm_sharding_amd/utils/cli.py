@@ -50,6 +50,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_gpus", type=int, default=None, help="GPUs to use (default: all visible; 0 = CPU)")
     p.add_argument("--prefix_attention", choices=["bidirectional", "causal"], default="bidirectional",
                    help="prefix self-attention: reference-compatible bidirectional (default) or causal")
+    p.add_argument("--sliding_window_mode", choices=["error", "apply"], default="error",
+                   help="models with a sliding window (Mistral, Mixtral, Phi-3, Qwen with use_sliding_window) and a "
+                        "prompt longer than it: error (default) refuses the call; apply runs sliding-window "
+                        "attention (a query sees the last sliding_window positions, its own included; calls that "
+                        "fit the window run unchanged)")
     p.add_argument("--hip_graphs", type=str2bool, nargs="?", const=True, default=False,
                    help="with --resident: capture each micro-batch's whole forward as one HIP graph and "
                         "replay it (shape-bucketed; removes per-op host dispatch for small batches)")
