@@ -155,6 +155,11 @@ int fls_rmsnorm(const void* x, const void* w, void* y, const int* row_idx, int r
                 int ldx, int ldy, float eps, fls_stream_t s);
 int fls_embed(const int* ids, const void* table, void* out, int T, int H, int V, float scale, fls_stream_t s);
 int fls_softmax_rows(const void* logits, void* probs, int rows, int V, float inv_scale, fls_stream_t s);
+// out[rows, 2] fp32 = (l[t] - logsumexp(l), l[t] == max(l)) per row of fp16 logits (row stride ld),
+// t = targets[row], l = the logits (inv_scale != 1: fp16(logit * inv_scale)).  The logits must be
+// finite.  A target outside [0, V) is never read: that row gets (-inf, 0).
+int fls_logprob_rows(const void* logits, int ld, int rows, int V, const int* targets, float inv_scale, float* out,
+                     fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0

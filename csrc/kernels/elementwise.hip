@@ -1,5 +1,5 @@
 // Memory-bound kernels (gfx950): RMSNorm (optionally row-gathered), token
-// embedding gather, vocab softmax, synthetic weight fill, weight dtype casts,
+// embedding gather, vocab softmax, target log-probability, synthetic weight fill, weight dtype casts,
 // skinny-M GEMV.
 // All loads/stores are 16-byte vectors (guide G13: scalar fp16 loads cost
 // ~2x); one 256-thread block per row; fp32 statistics.
@@ -220,6 +220,62 @@ __global__ __launch_bounds__(256) void softmax_kernel(const half_t* __restrict__
     }
   } else {
     for (int c = threadIdx.x; c < V; c += 256) pr[c] = (half_t)(__expf(ld(lr[c]) - gm) * inv);
+  }
+}
+
+// log-probability of one target column per row of fp16 logits (continuation log-likelihood
+// scoring): out[2r] = l[t] - logsumexp(l) in fp32, out[2r + 1] = 1 if l[t] is the row's maximum
+// (ties count), else 0.  The row is read once: each lane keeps an online max and sum as in pass 1
+// of softmax_kernel, and the lane that loads column t keeps l[t]; nothing of size V is written.
+// inv_scale != 1: l = fp16(logit * inv_scale), softmax_kernel's rounding.  A target outside
+// [0, V) matches no column, so it is never dereferenced: the row gets -inf and flag 0.
+// The logits must be finite (an infinite maximum would make m - nm a NaN).
+template <bool VEC>   // 16-byte loads: V % 8 == 0, ld % 8 == 0 and a 16-byte aligned base
+__global__ __launch_bounds__(256) void logprob_rows_kernel(const half_t* __restrict__ logits, int ld, int V,
+                                                         const int* __restrict__ targets, float inv_scale,
+                                                         float* __restrict__ out) {
+  const bool scaled = inv_scale != 1.f;
+  auto lg = [=](half_t h) { return scaled ? (float)(half_t)((float)h * inv_scale) : (float)h; };
+  __shared__ float red[4];
+  const half_t* lr = logits + (size_t)blockIdx.x * ld;
+  const int t = targets[blockIdx.x];
+  float m = -INFINITY, s = 0.f, lt = -INFINITY;
+  if (VEC) {
+    const int tc = t >> 3, tj = t & 7;               // (t < 0: tc < 0 matches no chunk)
+    for (int c = threadIdx.x; c < V / 8; c += 256) {
+      const half8 v = *(const half8*)(lr + c * 8);
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = lg(v[j]);
+      float vm = f[0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) vm = fmaxf(vm, f[j]);
+      const float nm = fmaxf(m, vm);
+      s *= __expf(m - nm);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += __expf(f[j] - nm);
+      m = nm;
+      if (c == tc) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lt = j == tj ? f[j] : lt;
+      }
+    }
+  } else {
+    for (int c = threadIdx.x; c < V; c += 256) {
+      const float v = lg(lr[c]);
+      const float nm = fmaxf(m, v);
+      s = s * __expf(m - nm) + __expf(v - nm);
+      m = nm;
+      if (c == t) lt = v;
+    }
+  }
+  const float gm = block_max(m, red);
+  const float gs = block_sum(m == -INFINITY ? 0.f : s * __expf(m - gm), red);
+  const float glt = block_max(lt, red);              // one lane holds l[t], the others -inf
+  if (threadIdx.x == 0) {
+    const bool ok = t >= 0 && t < V;
+    out[2 * (size_t)blockIdx.x] = ok ? glt - gm - logf(gs) : -INFINITY;
+    out[2 * (size_t)blockIdx.x + 1] = (ok && glt == gm) ? 1.f : 0.f;
   }
 }
 
@@ -469,6 +525,21 @@ extern "C" int fls_softmax_rows(const void* logits, void* probs, int rows, int V
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(softmax_kernel, dim3(rows), dim3(256), 0, (hipStream_t)s, (const half_t*)logits,
                      (half_t*)probs, V, inv_scale);
+  FLS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int fls_logprob_rows(const void* logits, int ld, int rows, int V, const int* targets, float inv_scale,
+                                float* out, fls_stream_t s) {
+  if (rows <= 0) return 0;
+  if (V <= 0 || ld < V) return -2;
+  const bool vec = V % 8 == 0 && ld % 8 == 0 && ((uintptr_t)logits & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(logprob_rows_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const half_t*)logits,
+                       ld, V, targets, inv_scale, out);
+  else
+    hipLaunchKernelGGL(logprob_rows_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const half_t*)logits,
+                       ld, V, targets, inv_scale, out);
   FLS_CHECK_LAUNCH();
   return 0;
 }

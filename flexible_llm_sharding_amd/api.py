@@ -33,7 +33,7 @@ from .parallel.comm import Comm
 from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
-from .utils.cli import parse_args
+from .utils.cli import check_score_mode, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -181,6 +181,9 @@ def resolve_hbm_cache_gb(args, cfg: ModelConfig, device: torch.device, reserve: 
 def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) -> ShardedRunner:
     device = torch.device(device)
     from .models.layout import layer_kind
+    check_score_mode(args)             # (args built without parse_args too)
+    if getattr(args, "score_mode", "next_token") == "loglik" and comm.world > 1 and not args.data_parallel:
+        raise ValueError("--score_mode loglik does not combine with model parallel: pass --data_parallel")
     pkv = resolve_prefix_kv_cache(args)
     skv = resolve_suffix_kv_cache(args, comm.world) and pkv
     n_dec = sum(1 for n in cfg.layer_names() if layer_kind(n) == "decoder")
@@ -233,6 +236,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          pipeline_stages=getattr(args, "pipeline_stages", "round_robin"),
                          rx_window=getattr(args, "rx_window", 2),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
+                         score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None))
 
 
@@ -260,10 +264,22 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
     # data parallel with all-gathered weights: every rank runs num_batch passes, even over an
     # empty slice, so the weight collectives line up across ranks
     collective = getattr(runner.prefetcher, "collective", False)
+    loglik = getattr(runner, "loglik", False)
     outs: List[np.ndarray] = []
+    toks: list = []                    # loglik: every prompt's per-token log-probabilities
     for b0, b1 in batch_ranges(len(mine), args.num_batch):
         if b1 > b0 or collective:
             outs += runner(mine[b0:b1])
+            if loglik:
+                toks += runner.last_token_logprobs
+    if loglik:
+        # a few floats per prompt: gathered as objects (gather_scores packs fp16 and would round
+        # them); rank 0's runner then holds the whole call's per-token values, in prompt order
+        allv = comm.gather_object((outs, toks), dst=0)
+        if comm.rank != 0:
+            return []
+        runner.last_token_logprobs = sum((t for _, t in allv), [])
+        return sum((o for o, _ in allv), [])
     if comm.world == 1:
         return outs
     allv = comm.gather_scores(outs, dst=0)
@@ -376,7 +392,15 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     t_build = time.perf_counter() - t0
     t1 = time.perf_counter()
     step_times: List[float] = []
-    scores, updated = generation_loop(args, runner, comm, tok, original, step_times)
+    if getattr(args, "score_mode", "next_token") == "loglik":
+        # one scoring pass, no greedy token to append: the prompts are written back as they came;
+        # the output file holds the [n_s, 3] arrays and the per-token log-probabilities
+        summary = run_all(args, runner, comm, list(original))
+        scores = {"scores": summary, "token_logprobs": list(runner.last_token_logprobs) if comm.rank == 0 else []}
+        updated = copy.deepcopy(list(original))
+        step_times.append(time.perf_counter() - t1)
+    else:
+        scores, updated = generation_loop(args, runner, comm, tok, original, step_times)
     t_run = time.perf_counter() - t1
     tokens = comm.all_reduce_sum(runner.stats.get("tokens", 0.0)) if not (
         comm.world > 1 and not args.data_parallel) else runner.stats.get("tokens", 0.0)

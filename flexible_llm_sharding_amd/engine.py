@@ -79,9 +79,25 @@ class ShardedRunner:
                  prefix_kv_cache: bool = False, prefix_cache_entries: int = 8, suffix_kv_cache: bool = False,
                  prune_last_layer: bool = True, pipeline_stages: str = "round_robin",
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
-                 exact_reuse: bool = True, sliding_window_mode: str = "error"):
+                 exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token"):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
+        if score_mode not in ("next_token", "loglik"):
+            raise ValueError(f"score_mode={score_mode!r}: 'next_token' or 'loglik'")
+        self.score_mode = score_mode
+        self.loglik = score_mode == "loglik"
+        if self.loglik:
+            # continuation log-likelihood: every suffix token is scored in one full pass; the paths
+            # that replay, reuse or hand over parts of a pass are not wired for it
+            world = comm.world if comm is not None else 1
+            for on, flag in ((hip_graphs, "--hip_graphs"), (prefix_kv_cache, "--prefix_kv_cache"),
+                             (suffix_kv_cache, "--suffix_kv_cache"), (resume_dir, "--resume_dir"),
+                             (world > 1 and not data_parallel,
+                              "model parallel (several GPUs without --data_parallel)")):
+                if on:
+                    raise ValueError(f"--score_mode loglik does not combine with {flag}")
+        # last call's per-token log-probabilities (loglik): per prompt a list of n_s float32 arrays
+        self.last_token_logprobs: List[Optional[List[np.ndarray]]] = []
         self.sliding_window_mode = sliding_window_mode
         self.cfg = cfg
         self.src = source
@@ -187,7 +203,10 @@ class ShardedRunner:
         self.ctx = ExecContext(cfg, self.ops, self.dev, self.act_dtype, cos, sin, mlp_chunk, qkv_chunk=qkv_chunk,
                                attn_rows=attn_rows)
         decs = [n for n in self.names if layer_kind(n) == "decoder"]
-        self.ctx.prune_last = bool(prune_last_layer and decs)
+        # (loglik scores rows of every suffix position and the last prefix row: the last decoder
+        # layer computes every row, and the final norm gathers the scored ones)
+        self.ctx.prune_last = bool(prune_last_layer and decs and not self.loglik)
+        self.ctx.loglik = self.loglik
         self.ctx.last_decoder = decs[-1] if decs else ""
         my = [s for s in self.plan.my_shards if len(s)]
         self.my_shards = my
@@ -286,11 +305,15 @@ class ShardedRunner:
             return (batch.num_tokens, self.cfg.hidden_size)
         if kind == "norm":
             return (batch.n_scored, self.cfg.hidden_size)
+        if self.loglik:
+            return (batch.n_scored, 2)         # fp32 (log-probability, greedy flag) per pair
         return (batch.n_scored, self.cfg.vocab_size)
 
     # ------------------------------------------------------------- main
     def __call__(self, prompts) -> List[np.ndarray]:
-        """Reference API: list of (prefix, suffixes) -> list of [n_s, 1, V] fp16 arrays."""
+        """Reference API: list of (prefix, suffixes) -> list of [n_s, 1, V] fp16 arrays.
+        ``score_mode="loglik"``: list of [n_s, 3] float32 arrays (log p(suffix | prefix), its token
+        count, 1.0 if every token is the greedy one), per-token values in ``last_token_logprobs``."""
         if self.my_shards and prompts and not self.resume_dir and not self.hip_graphs:
             # the first shards' weights do not depend on the prompts: their H2D overlaps tokenization
             if self._h2d0 is None:
@@ -434,6 +457,19 @@ class ShardedRunner:
                              "sliding-window attention is not implemented")
         return int(sw)
 
+    def _check_loglik(self, tps) -> None:
+        """A loglik call's targets, validated on the host before any launch: every suffix has a
+        real token (its first is scored at the last prefix row), every id is a vocabulary row."""
+        V = self.cfg.vocab_size
+        for i, tp in enumerate(tps):
+            if not tp.prefix:
+                raise ValueError(f"score_mode='loglik': prompt {i} has an empty prefix")
+            for s, (ids, e) in enumerate(zip(tp.suffixes, tp.eos_index)):
+                if e < 0 or not ids:
+                    raise ValueError(f"score_mode='loglik': suffix {s} of prompt {i} has no token to score")
+                if min(ids) < 0 or max(ids) >= V:
+                    raise ValueError(f"score_mode='loglik': suffix {s} of prompt {i} holds a token id outside [0, {V})")
+
     def run_tokenized(self, tps: Sequence[TokenizedPrompt]) -> List[Optional[np.ndarray]]:
         t_start = time.perf_counter()
         spec, self._spec = self._spec, None
@@ -442,6 +478,10 @@ class ShardedRunner:
                 return self._finish_spec(spec, tps, t_start)
             self._drop_spec(spec)
         n = len(tps)
+        if self.loglik:
+            self._check_loglik(tps)
+            self._pair_lens = [[len(s) for s in tp.suffixes] for tp in tps]
+            self.last_token_logprobs = [None] * n
         window = self._call_window(tps)
         entry, cached = self._prefix_entry(tps)
         if self._vram_cap:
@@ -459,7 +499,7 @@ class ShardedRunner:
                                 kv_cached=cached, q_block=self.q_block,
                                 suffix_rows=[sfx_rows[i] for i in g] if sfx_rows is not None else None,
                                 suffix_keep=[sfx_keep[i] for i in g] if sfx_keep is not None else None,
-                                single_suffix_items=self.row_exact, window=window)
+                                single_suffix_items=self.row_exact, window=window, loglik=self.loglik)
                    for g in groups]
         t_pack = time.perf_counter() - t_start
         if self.hip_graphs:
@@ -508,7 +548,13 @@ class ShardedRunner:
                                         overhead=self._outside,
                                         weight_bytes=self.prefetcher.planned_hbm_bytes() if self.cuda else None,
                                         fused_norm=self.ctx.fused_norm, extra_bytes=stage,
-                                        grouped=self.prefix_cache is None)
+                                        grouped=self.prefix_cache is None,
+                                        scored_rows=sum(len(s) for tp in tps for s in tp.suffixes) if self.loglik else 0)
+        if self.loglik and self.ctx.ws is not None and (mc, ar, qc) != (self.ctx.mlp_chunk, self.ctx.attn_rows,
+                                                                          self.ctx.qkv_chunk):
+            # the norm state grows with the call's scored pairs and the plan shrinks the chunks to
+            # make room: an arena kept from a call planned with larger chunks would overrun the cap
+            self.ctx.ws.buf = None
         self.token_budget, self.mlp_chunk = tb, mc
         self.ctx.mlp_chunk, self.ctx.attn_rows, self.ctx.qkv_chunk = mc, ar, qc
         # (the plan charged ceil(total / tb) states; a split that needs more micro-batches — whole
@@ -1275,6 +1321,8 @@ class ShardedRunner:
     def _collect(self, batch: PackedBatch, probs: np.ndarray, am, outputs) -> None:
         """Host scores of a finished micro-batch into ``outputs`` (prompt order) and its greedy
         tokens into ``self.last_tokens`` (``am``: the rows' argmax, computed on the device)."""
+        if self.loglik:
+            return self._collect_loglik(batch, probs, outputs)
         am = am.numpy() if am is not None else None
         r = 0
         for j, pid in enumerate(batch.prompt_ids):
@@ -1284,12 +1332,35 @@ class ShardedRunner:
                 self.last_tokens[pid] = am[r:r + ns].astype(np.int64).reshape(ns, 1)
             r += ns
 
+    def _collect_loglik(self, batch: PackedBatch, pairs: np.ndarray, outputs) -> None:
+        """The [n_pairs, 2] (log-probability, greedy flag) rows of a finished micro-batch split back
+        into suffixes (pairs are in prompt -> suffix -> token order): per prompt the [n_s, 3] float32
+        (sum, token count, all-greedy) into ``outputs`` — sums in float64 — and the per-token
+        values into ``self.last_token_logprobs``."""
+        r = 0
+        for j, pid in enumerate(batch.prompt_ids):
+            s0, s1 = (int(v) for v in batch.prompt_scored[j])
+            lens = self._pair_lens[pid]
+            assert s0 == r and s1 - s0 == sum(lens), (s0, s1, r, lens)
+            out = np.empty((len(lens), 3), dtype=np.float32)
+            per_tok = []
+            for s, n in enumerate(lens):
+                lp = pairs[r:r + n, 0].astype(np.float32, copy=True)
+                out[s] = (lp.astype(np.float64).sum(), n, float(bool((pairs[r:r + n, 1] == 1.0).all())))
+                per_tok.append(lp)
+                r += n
+            outputs[pid] = out
+            self.last_token_logprobs[pid] = per_tok
+
     def _start_output_copy(self, batch: PackedBatch, probs: torch.Tensor):
         """D2H of a micro-batch's probabilities and of their row argmax (the greedy token of
         each suffix: api.generation_loop needs no host pass over the [n_s, V] scores)."""
-        am = self.ops.argmax_rows(probs) if hasattr(self.ops, "argmax_rows") else None
+        if self.loglik:
+            am = None                 # probs: the fp32 [n_pairs, 2] head state, copied as it is
+        else:
+            am = self.ops.argmax_rows(probs) if hasattr(self.ops, "argmax_rows") else None
         if not self.cuda:
-            return batch, probs.detach().to(torch.float16).cpu(), None, None, am
+            return batch, probs.detach().to(torch.float32 if self.loglik else torch.float16).cpu(), None, None, am
         store = self._get_store()
         nbytes = probs.numel() * probs.element_size()
         pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])

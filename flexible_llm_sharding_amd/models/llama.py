@@ -195,6 +195,11 @@ class ExecContext:
     # generation with the K/V caches (engine "exact K/V reuse"): every row's arithmetic independent
     # of the other rows of the call (row-exact GEMM paths, the row statistic from the row itself)
     row_exact: bool = False
+    # continuation log-likelihood scoring (engine score_mode="loglik"): the head reduces each scored
+    # row's logits to the log-probability of meta["targets"], head_chunk rows of logits at a time
+    # (0: as many as the arena, or 64 MB, holds)
+    loglik: bool = False
+    head_chunk: int = 0
     ss_buf: Optional[torch.Tensor] = None      # the arena-backed buffer (grown, reused)
     ss_cur: Optional[torch.Tensor] = None      # the buffer the last residual GEMM wrote
     ss_key: Optional[tuple] = None
@@ -603,7 +608,20 @@ def run_norm(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, meta
     return ctx.ops.gather_rmsnorm(x, meta["last_idx"], W["norm"], ctx.cfg.rms_norm_eps)
 
 
-def run_head(ctx: ExecContext, W: Dict[str, torch.Tensor], h: torch.Tensor) -> torch.Tensor:
+def run_head(ctx: ExecContext, W: Dict[str, torch.Tensor], h: torch.Tensor, meta: Optional[dict] = None) -> torch.Tensor:
+    if ctx.loglik:
+        # [n_pairs, 2] fp32 (log-probability of each pair's target, greedy flag): the logits exist
+        # one row chunk at a time, in the workspace arena (idle in the norm and head phase)
+        scratch, V, ws = None, W["head"].shape[0], ctx.ws
+        if ws is not None and ws.buf is not None:
+            # as much of the arena as the rows need, never grown; a small-M head GEMM's split-K
+            # partials then go to the free tail behind the chunk (engine._splitk_scratch)
+            ws.reset()
+            n = min(h.shape[0], ctx.head_chunk or h.shape[0], (ws.buf.numel() - 127) // V)
+            if n > 0:
+                scratch = ws.take(n, V).view(-1)
+        return ctx.ops.lm_head_logprob(h, W["head"], meta["targets"], logits_scaling=ctx.cfg.logits_scaling,
+                                       chunk_rows=ctx.head_chunk, scratch=scratch)
     return ctx.ops.lm_head_softmax(h, W["head"], logits_scaling=ctx.cfg.logits_scaling)
 
 
@@ -616,7 +634,7 @@ def run_layer(ctx: ExecContext, layer_name: str, W: Dict[str, torch.Tensor],
         return run_decoder(ctx, W, state, batch, meta, layer_name)
     if kind == "norm":
         return run_norm(ctx, W, state, meta)
-    return run_head(ctx, W, state)
+    return run_head(ctx, W, state, meta)
 
 
 def layer_flops(cfg: ModelConfig, batch, pruned: bool = False) -> float:

@@ -104,12 +104,53 @@ def reference_scores(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts
     position j is visible to a query at position i only if i - j < W (W keys, the row's own
     included: the rule of transformers 5.x); the window only cuts off the past, so bidirectional
     prefix queries still see every later prefix key."""
+    outs = []
+    for P, S, sids, eos in _forward(cfg, sd, tok, prompts, prefix_attention, max_len, cos, sin):
+        ns = sids.shape[0]
+        last = S[torch.arange(ns), eos][:, None]                             # utils.py:286
+        outs.append(torch.softmax(_logits(cfg, sd, last)[:, 0], -1)[:, None].numpy())
+    return outs
+
+
+def _logits(cfg: ModelConfig, sd: Dict[str, torch.Tensor], x: torch.Tensor) -> torch.Tensor:
+    """Final norm + LM head (+ Granite's logits scaling) of hidden rows x [..., H]."""
+    h = _rms(x, sd["model.norm.weight"].float(), cfg.rms_norm_eps)
+    head = sd.get("lm_head.weight", sd["model.embed_tokens.weight"]).float()
+    return (h @ head.t()) / cfg.logits_scaling
+
+
+def reference_logliks(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence,
+                      prefix_attention: str = "bidirectional", max_len: int = 4096,
+                      cos=None, sin=None, dists: bool = False) -> List[List[np.ndarray]]:
+    """Per prompt, per suffix: float64 [L] log p(u[t] | prefix, u[:t]) of the suffix's L real tokens
+    u, from the forward of :func:`reference_scores`: token 0 is scored at the last prefix row,
+    token t >= 1 at suffix row t - 1 (log-softmax in float64 of the fp32 logits).  ``dists``: the
+    whole [L, V] log-distribution of every scored row instead of its target's entry."""
+    outs = []
+    for P, S, sids, eos in _forward(cfg, sd, tok, prompts, prefix_attention, max_len, cos, sin):
+        lp_pre = torch.log_softmax(_logits(cfg, sd, P[0, -1]).double(), -1)          # [V]
+        lp_suf = torch.log_softmax(_logits(cfg, sd, S).double(), -1)                 # [ns, Ls, V]
+        per = []
+        for s in range(sids.shape[0]):
+            L = int(eos[s]) + 1
+            if L < 1:
+                raise ValueError(f"suffix {s} has no real token")
+            u = sids[s, :L]
+            rows = torch.cat([lp_pre[None], lp_suf[s, :L - 1]])                       # [L, V]
+            per.append(rows.numpy() if dists else rows[torch.arange(L), u].numpy())
+        outs.append(per)
+    return outs
+
+
+def _forward(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence, prefix_attention: str,
+             max_len: int, cos, sin):
+    """Per prompt: (prefix hidden states [1, Lp, H], suffix hidden states [n_s, Ls, H] after the
+    last decoder layer, the padded suffix ids [n_s, Ls], the reference's suffix_eos [n_s])."""
     from .llama import rope_tables
     from ..utils.synthetic import split_projections
     sd = split_projections(cfg, sd)          # Phi-3 fused qkv_proj / gate_up_proj -> split names
     if cos is None:
         cos, sin = rope_tables(cfg, max_len)
-    outs = []
     neg = torch.finfo(torch.float32).min
     for prefix, suffixes in prompts:
         pids = torch.tensor(tok(prefix, truncation=True, max_length=max_len)["input_ids"])[None]
@@ -136,9 +177,4 @@ def reference_scores(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts
             P, (kc, vc) = _block(P, sd, p, cfg, ppos, cos, sin, pmask)
             kv = (kc.expand(ns, -1, -1, -1), vc.expand(ns, -1, -1, -1))
             S, _ = _block(S, sd, p, cfg, spos, cos, sin, smask, past_kv=kv)
-        last = S[torch.arange(ns), eos][:, None]                             # utils.py:286
-        h = _rms(last, sd["model.norm.weight"].float(), cfg.rms_norm_eps)
-        head = sd.get("lm_head.weight", sd["model.embed_tokens.weight"]).float()
-        logits = (h @ head.t())[:, 0] / cfg.logits_scaling
-        outs.append(torch.softmax(logits, -1)[:, None].numpy())
-    return outs
+        yield P, S, sids, eos

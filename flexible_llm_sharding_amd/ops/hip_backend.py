@@ -26,6 +26,7 @@ ROW_EXACT = 0x100                  # csrc/include/fls.h: the row-exact epi flag
 SPLITK_MAX_M = 512                 # csrc/kernels/gemm.hip SPLITK_MAX_M
 SPLITK_WS_BYTES = 64 << 20        # fp32 partial slabs: e.g. 8 slices x 160 rows x 10240 columns
 CAST_BF16, CAST_F32 = 1, 2
+LOGPROB_CHUNK_BYTES = 64 << 20    # lm_head_logprob without an arena: logits alive at once
 
 
 def _stream():
@@ -520,6 +521,51 @@ class HipOps:
 
     def lm_head_softmax(self, h, w, logits_scaling: float = 1.0):
         return self.softmax(self.linear(h, w), logits_scaling)
+
+    def logprob_rows(self, logits, targets, logits_scaling: float = 1.0, out=None):
+        """[rows, 2] fp32: (l[t] - logsumexp(l), 1.0 if l[t] == max(l) else 0.0) per row of finite fp16
+        logits, t = targets[row] (int32, in [0, V): the caller validates them; the kernel gives an
+        outside one -inf and never reads it), l = the logits (logits_scaling != 1:
+        fp16(logits / logits_scaling), :meth:`softmax`'s rounding).  One pass over the row."""
+        _f16(logits, "logits")
+        rows, V = logits.shape
+        if targets.dtype != torch.int32 or not targets.is_cuda or not targets.is_contiguous() or targets.numel() != rows:
+            raise TypeError(f"targets must be a contiguous int32 CUDA vector of {rows} entries")
+        if out is None:
+            out = torch.empty(rows, 2, dtype=torch.float32, device=logits.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (rows, 2) or not out.is_contiguous():
+            raise TypeError(f"out must be a contiguous fp32 [{rows}, 2] tensor")
+        _chk(self.k.fls_logprob_rows(logits.data_ptr(), logits.stride(0), rows, V, targets.data_ptr(),
+                                     1.0 / float(logits_scaling), out.data_ptr(), _stream()), "fls_logprob_rows")
+        return out
+
+    def lm_head_logprob(self, h, w, targets, logits_scaling: float = 1.0, chunk_rows: int = 0, scratch=None):
+        """:meth:`logprob_rows` of the LM head's logits, head GEMM -> row reduction over chunks of
+        ``chunk_rows`` rows, so only one chunk of logits exists at a time and no [rows, V] tensor is
+        ever written.  A chunk is at most ``LOGPROB_CHUNK_BYTES`` of logits.  ``scratch``: an fp16
+        buffer the chunk lives in (the idle workspace arena; its size bounds the chunk too), else
+        it is allocated.  ``chunk_rows`` > 0 lowers the bound further (tests).  The GEMMs take the
+        row-exact paths (:meth:`row_exact`), so a row's value does not depend on how the rows are
+        chunked or split into micro-batches (a VRAM cap changes both)."""
+        rows, V = h.shape[0], w.shape[0]
+        out = torch.empty(rows, 2, dtype=torch.float32, device=h.device)
+        if rows == 0:
+            return out
+        step = max(1, LOGPROB_CHUNK_BYTES // (2 * V))
+        if scratch is not None and scratch.numel() >= V:
+            step = min(step, scratch.numel() // V)
+        else:
+            scratch = None
+        step = min(rows, step, chunk_rows if chunk_rows > 0 else rows)
+        if scratch is None:
+            scratch = torch.empty(step * V, dtype=torch.float16, device=h.device)
+        with self.row_exact(True):
+            for s in range(0, rows, step):
+                n = min(step, rows - s)
+                logits = scratch[:n * V].view(n, V)
+                self.gemm(h[s:s + n], w, out=logits)
+                self.logprob_rows(logits, targets[s:s + n], logits_scaling, out=out[s:s + n])
+        return out
 
     def cast_f16(self, dst: torch.Tensor, src: torch.Tensor, src_code: int) -> None:
         """dst (fp16 bytes) = fp16(src bytes of bf16 (code 1; may be in place) or fp32 (code 2))."""

@@ -210,6 +210,28 @@ class TorchOps:
         logits = (self._c(h) @ self._c(w).t()).to(h.dtype)   # fp16 logits like nn.Linear in fp16
         return self.softmax(logits, logits_scaling)
 
+    def logprob_rows(self, logits: torch.Tensor, targets: torch.Tensor, logits_scaling: float = 1.0) -> torch.Tensor:
+        """[rows, 2] fp32: (l[t] - logsumexp(l), l[t] == max(l)) with l the rows :meth:`softmax`
+        normalises (fp16-rounded where the activations are fp16) and t = targets[row]."""
+        if logits_scaling != 1.0:
+            logits = logits / logits_scaling
+        l = logits.float()
+        lt = l.gather(1, targets.long()[:, None])[:, 0]
+        lp = torch.log_softmax(l, dim=-1).gather(1, targets.long()[:, None])[:, 0]
+        return torch.stack([lp, (lt == l.max(dim=-1).values).float()], dim=1)
+
+    def lm_head_logprob(self, h: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, logits_scaling: float = 1.0,
+                        chunk_rows: int = 0, scratch=None) -> torch.Tensor:
+        """HipOps.lm_head_logprob: head matmul -> :meth:`logprob_rows` in chunks of ``chunk_rows``
+        rows (0: all rows at once)."""
+        rows = h.shape[0]
+        step = min(rows, chunk_rows) if chunk_rows > 0 else rows
+        out = torch.empty(rows, 2, dtype=torch.float32, device=h.device)
+        for s in range(0, rows, max(step, 1)):
+            logits = (self._c(h[s:s + step]) @ self._c(w).t()).to(h.dtype)
+            out[s:s + step] = self.logprob_rows(logits, targets[s:s + step], logits_scaling)
+        return out
+
     def row_exact(self, on: bool = True):
         """HipOps.row_exact: nothing to select here (one matmul path)."""
         import contextlib

@@ -360,6 +360,7 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                          prefix_cache_entries=getattr(args, "prefix_cache_entries", 8),
                          suffix_kv_cache=_suffix_kv(args, comm), exact_reuse=getattr(args, "exact_reuse", True),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
+                         score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None))
 
 

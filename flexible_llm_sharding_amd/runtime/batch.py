@@ -97,6 +97,11 @@ class PackedBatch:
                                                 # kernel walks range 0 from the 64-key tile of the min,
                                                 # and masks by r0_lo the tiles that start below the max
     r0_item_last: Optional[np.ndarray] = None   # [S_total, 2] the same for ``work_last``
+    targets: Optional[np.ndarray] = None        # [n_pairs] int32, log-likelihood scoring: the token whose
+                                                # log-probability row ``last_idx[i]`` gives; ``last_idx`` and
+                                                # ``prompt_scored`` then range over (row, target) pairs
+                                                # (``last_segments`` / ``work_last`` stay per suffix: such a
+                                                # batch runs the unpruned last layer, which reads neither)
     _dev: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -197,7 +202,7 @@ class PackedBatch:
              "last_idx": self.last_idx, "last_pos": self.positions[self.last_idx].astype(np.int32),
              "work_last": self.work_last}
         for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win",
-                     "r0_lo", "r0_item", "r0_item_last"):
+                     "r0_lo", "r0_item", "r0_item_last", "targets"):
             v = getattr(self, name)
             if v is not None:
                 m[name] = v
@@ -219,7 +224,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                  kv_cached: bool = False, q_block: int = Q_BLOCK,
                  suffix_rows: Optional[Sequence[Sequence[int]]] = None,
                  suffix_keep: Optional[Sequence[Sequence[int]]] = None,
-                 single_suffix_items: bool = False, window: int = 0) -> PackedBatch:
+                 single_suffix_items: bool = False, window: int = 0, loglik: bool = False) -> PackedBatch:
     """Pack prompts into one token matrix + attention work items.
 
     ``prefix_offsets`` (rows of each prompt's prefix in a PrefixEntry) turns on
@@ -245,7 +250,15 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     ``work2`` start each item's walk at the 64-key tile of its rows' smallest bound (tiles stay at
     multiples of 64 keys from the unwindowed range start, so a row meets the same tiles in every
     step that computes it).
+
+    ``loglik``: continuation log-likelihood scoring.  ``last_idx`` / ``targets`` then hold one
+    (row, target) pair per suffix token, in prompt -> suffix -> token order: token 0 of a suffix is
+    scored at the prompt's last prefix row (repeated once per suffix), token t >= 1 at the suffix's
+    row t - 1; the last row of a suffix scores nothing.  Every suffix needs a token and every
+    prompt a prefix row; not with ``kv_cached`` or ``suffix_keep`` (the prefix rows are not packed).
     """
+    if loglik and (kv_cached or suffix_keep is not None):
+        raise ValueError("loglik packing does not combine with kv_cached / suffix_keep")
     if window < 0:
         raise ValueError(f"window={window}")
     W = int(window)
@@ -265,12 +278,15 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     r0_lo, r0_item, r0_item_last = [], [], []
     src, dst, sfx_src, sfx_dst = [], [], [], []
     p_rows, p_items, p_scored = [], [], []
+    pair_rows, pair_tgt, n_pairs = [], [], 0       # loglik: (row, target) pairs
     t = 0
     padded = 0
     max_pos = 0
     for j, tp in enumerate(tps):
         Lp = len(tp.prefix)
-        row0, item0, sc0 = t, len(work), len(last)
+        row0, item0, sc0 = t, len(work), (n_pairs if loglik else len(last))
+        if loglik and Lp == 0:
+            raise ValueError(f"loglik: prompt {prompt_ids[j]} has no prefix token to score a suffix's first token at")
         if kv_cached:
             p0 = prefix_offsets[j]
         else:
@@ -311,6 +327,14 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             r2s, r2l = (c0_row, c) if c else (0, 0)
             segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l, window=W))
             last.append(s0 + n - 1)
+            if loglik:
+                if n == 0:
+                    raise ValueError(f"loglik: suffix {si} of prompt {prompt_ids[j]} has no token")
+                rows = np.arange(s0 - 1, s0 + n - 1, dtype=np.int32)     # token t >= 1 at suffix row t - 1
+                rows[0] = p0 + Lp - 1                                    # token 0 at the last prefix row
+                pair_rows.append(rows)
+                pair_tgt.append(np.asarray(s, dtype=np.int32))
+                n_pairs += n
             # the scored row alone, for a last decoder layer that computes only scored rows
             lsegs.append(Segment(s0 + n - 1, 1, p0, Lp, 0, s0, n, q_off=n - 1, r2_start=r2s, r2_len=r2l,
                                  window=W))
@@ -360,7 +384,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         max_pos = max(max_pos, Lp + max([len(s) for s in tp.suffixes] or [0]))
         p_rows.append((row0, t))
         p_items.append((item0, len(work)))
-        p_scored.append((sc0, len(last)))
+        p_scored.append((sc0, n_pairs if loglik else len(last)))
         nsuf.append(tp.n_suffix)
         padded += tp.padded_tokens
     work = np.asarray(work, dtype=np.int32).reshape(-1, WORK_ITEM_FIELDS)
@@ -372,7 +396,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         prompt_ids=list(prompt_ids), n_suffix=nsuf,
         ids=cat(ids), positions=cat(pos),
         segments=segs, work=work, seg_lo=cat(seg_lo),
-        last_idx=np.asarray(last, dtype=np.int32), last_segments=lsegs,
+        last_idx=cat(pair_rows) if loglik else np.asarray(last, dtype=np.int32), last_segments=lsegs,
         work_last=(np.asarray(lwork, dtype=np.int32).reshape(-1, WORK_ITEM_FIELDS) if reuse
                    else _work_items(lsegs)), num_tokens=t, padded_tokens=padded,
         max_pos=max_pos, kv_cached=kv_cached, q_block=q_block,
@@ -389,7 +413,8 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         window=W,
         r0_lo=cat(r0_lo) if W else None,
         r0_item=np.asarray(r0_item, dtype=np.int32).reshape(-1, 2) if W else None,
-        r0_item_last=np.asarray(r0_item_last, dtype=np.int32).reshape(-1, 2) if W else None)
+        r0_item_last=np.asarray(r0_item_last, dtype=np.int32).reshape(-1, 2) if W else None,
+        targets=cat(pair_tgt) if loglik else None)
 
 
 def _items(sg: Segment, q_block: int = Q_BLOCK) -> List[tuple]:

@@ -150,14 +150,18 @@ def plan_for_vram(cfg: ModelConfig, max_vram_bytes: int, lnps: int = 1, n_slots:
                   total_tokens: Optional[int] = None, max_prompt_rows: int = 0,
                   overhead: Optional[int] = None, weight_bytes: Optional[int] = None,
                   fused_norm: bool = False, extra_bytes: int = 0,
-                  grouped: bool = True) -> Tuple[int, int, int, int, int, bool]:
+                  grouped: bool = True, scored_rows: int = 0) -> Tuple[int, int, int, int, int, bool]:
     """-> (token_budget, mlp_chunk, attn_rows, qkv_chunk, estimated peak bytes, resident) for a
     call of ``total_tokens`` packed tokens (None: unknown, assume several micro-batches) whose
     largest prompt has ``max_prompt_rows`` rows.  ``overhead``: device memory held outside the plan
     (measured context + code objects; default DEVICE_OVERHEAD); ``weight_bytes``: the weight
     buffers actually planned (default ``n_slots`` full-shard slots); ``extra_bytes``: other fixed
     device buffers (the host-mode prefix K/V cache's staging); ``grouped=False``: no prompt-aligned
-    attention groups (the prefix K/V cache runs the whole micro-batch).  ``resident``: every
+    attention groups (the prefix K/V cache runs the whole micro-batch); ``scored_rows``: rows of
+    the final norm's state when it is not small against the hidden state (log-likelihood scoring:
+    one row per suffix token of the call), charged as [scored_rows, H] on top of the hidden
+    states — every micro-batch's norm state may stay in HBM until its head runs; the head's logits
+    chunk lives in the arena and adds nothing.  ``resident``: every
     micro-batch's hidden state keeps an activation-ring slot of its own for the whole pass (no
     state is parked in host memory); else the ring has ``STATES`` slots.
 
@@ -174,6 +178,7 @@ def plan_for_vram(cfg: ModelConfig, max_vram_bytes: int, lnps: int = 1, n_slots:
     weights = weight_slot_bytes(cfg, lnps, n_slots) if weight_bytes is None else weight_bytes
     target = int(max_vram_bytes * (1.0 - CAP_MARGIN))
     over = (DEVICE_OVERHEAD if overhead is None else overhead) + extra_bytes
+    over += int(SLACK * 2 * scored_rows * cfg.hidden_size)
     best = None
     budgets = sorted({token_budget, 49152, 32768, 24576, 16384, 12288, 8192, 6144, 4096, 3072, 2048, 1024})
     # multiples of 3072 rows give whole 256-CU rounds of the 384-row GEMM tile (models/llama.py)

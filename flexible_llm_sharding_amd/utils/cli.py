@@ -55,6 +55,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "prompt longer than it: error (default) refuses the call; apply runs sliding-window "
                         "attention (a query sees the last sliding_window positions, its own included; calls that "
                         "fit the window run unchanged)")
+    p.add_argument("--score_mode", choices=["next_token", "loglik"], default="next_token",
+                   help="next_token (default): the next-token distribution after each suffix ([n_s, 1, V] fp16 per "
+                        "prompt).  loglik: log p(suffix | prefix), summed over the suffix's tokens in one pass "
+                        "([n_s, 3] float32 per prompt: the sum, the token count, 1 if every token is the greedy "
+                        "one); --output_file then holds the per-token log-probabilities.  Not with --num_gen_token "
+                        "> 1, --hip_graphs, --prefix_kv_cache / --suffix_kv_cache true, --resume_dir or model "
+                        "parallel")
     p.add_argument("--hip_graphs", type=str2bool, nargs="?", const=True, default=False,
                    help="with --resident: capture each micro-batch's whole forward as one HIP graph and "
                         "replay it (shape-bucketed; removes per-op host dispatch for small batches)")
@@ -125,5 +132,21 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def check_score_mode(args) -> None:
+    """``--score_mode loglik`` refuses what it is not built for, naming the flag (``auto`` K/V
+    caches resolve to off: they follow ``--num_gen_token``, which must be 1)."""
+    if getattr(args, "score_mode", "next_token") != "loglik":
+        return
+    for bad, flag in ((getattr(args, "num_gen_token", 1) != 1, "--num_gen_token other than 1"),
+                      (getattr(args, "hip_graphs", False), "--hip_graphs"),
+                      (getattr(args, "prefix_kv_cache", False) is True, "--prefix_kv_cache true"),
+                      (getattr(args, "suffix_kv_cache", False) is True, "--suffix_kv_cache true"),
+                      (getattr(args, "resume_dir", None), "--resume_dir")):
+        if bad:
+            raise ValueError(f"--score_mode loglik does not combine with {flag}")
+
+
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    args = build_parser().parse_args(argv)
+    check_score_mode(args)
+    return args
