@@ -160,6 +160,12 @@ int fls_softmax_rows(const void* logits, void* probs, int rows, int V, float inv
 // finite.  A target outside [0, V) is never read: that row gets (-inf, 0).
 int fls_logprob_rows(const void* logits, int ld, int rows, int V, const int* targets, float inv_scale, float* out,
                      fls_stream_t s);
+// out[r] = the sampled token of row r of fp16 probabilities (row stride ld, V < 2^18): temperature
+// through table (15,361 uint32 weights indexed by the fp16 bit pattern 0 .. 0x3C00, non-decreasing),
+// top_k (0: off), top-p as P = round(top_p * 65536) in [1, 65536], one uint64 draw per row.
+// Integer-exact (csrc/kernels/sampling.hip); top_k = 1 or P = 1 gives fls_argmax_rows' token.
+int fls_sample_rows(const void* probs, int ld, int rows, int V, const uint32_t* table, const uint64_t* draws,
+                    int top_k, int P, int* out, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0

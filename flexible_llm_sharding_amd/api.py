@@ -33,7 +33,8 @@ from .parallel.comm import Comm
 from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
-from .utils.cli import check_score_mode, parse_args
+from .sampling import SamplingParams, draws as sample_draws, sample_tokens
+from .utils.cli import check_sampling, check_score_mode, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -182,6 +183,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     device = torch.device(device)
     from .models.layout import layer_kind
     check_score_mode(args)             # (args built without parse_args too)
+    check_sampling(args)
     if getattr(args, "score_mode", "next_token") == "loglik" and comm.world > 1 and not args.data_parallel:
         raise ValueError("--score_mode loglik does not combine with model parallel: pass --data_parallel")
     pkv = resolve_prefix_kv_cache(args)
@@ -237,7 +239,10 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          rx_window=getattr(args, "rx_window", 2),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          score_mode=getattr(args, "score_mode", "next_token"),
-                         max_vram_gb=getattr(args, "max_vram_gb", None))
+                         max_vram_gb=getattr(args, "max_vram_gb", None),
+                         # one rank draws the tokens on the device; several ranks: rank 0 draws the
+                         # same tokens on the host from the gathered scores (generation_loop)
+                         sampling=SamplingParams.from_args(args) if comm.world == 1 else None)
 
 
 def load_model_meta(args):
@@ -269,6 +274,7 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
     toks: list = []                    # loglik: every prompt's per-token log-probabilities
     for b0, b1 in batch_ranges(len(mine), args.num_batch):
         if b1 > b0 or collective:
+            runner.prompt_base = b0        # (sampling on one rank: the draws take the prompt-file index)
             outs += runner(mine[b0:b1])
             if loglik:
                 toks += runner.last_token_logprobs
@@ -297,8 +303,12 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
 def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, step_times: Optional[list] = None):
     """main.py:63-90 — greedy extension of every suffix, one full pass per step (the prefix K/V
     cache and the HBM weight cache, on by default for repeated passes, make the later passes
-    cheaper; the scores are the same).  ``step_times`` collects each step's wall time."""
+    cheaper; the scores are the same).  ``step_times`` collects each step's wall time.
+    ``--do_sample``: the appended token is drawn from the step's scores instead (sampling.py), on
+    the device where the runner holds every prompt, else here on rank 0: the same tokens."""
     input_prompts = copy.deepcopy(list(original_prompts))
+    sampling = SamplingParams.from_args(args)
+    table = sampling.table() if sampling is not None and comm.rank == 0 else None
     # per prompt: every step's [n_s, 1, V] scores and argmax tokens.  The reference concatenates the
     # scores each step and takes the argmax over all of them (main.py:83-88); the argmax of the
     # earlier steps cannot change, so each step's is taken once, and the scores are concatenated
@@ -319,6 +329,7 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
         t_step = time.perf_counter()
         if hasattr(runner, "spec_steps"):
             runner.spec_steps = (args.num_gen_token - 1 - i_new) if spec else 0
+        runner.sample_step = i_new
         prof = None
         if i_new in prof_steps:
             import cProfile
@@ -334,7 +345,14 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
             prof.disable()
             prof.dump_stats(f"gen_profile.{i_new}")
         if comm.rank == 0:
-            toks = dev_tok if dev_tok is not None else [greedy_tokens(o) for o in outputs]
+            if dev_tok is not None:
+                toks = dev_tok
+            elif sampling is None:
+                toks = [greedy_tokens(o) for o in outputs]
+            else:
+                toks = [sample_tokens(o[:, 0, :], table, sampling.top_k, sampling.P,
+                                      sample_draws(sampling.seed, [pi], [o.shape[0]], i_new)).reshape(-1, 1)
+                        for pi, o in enumerate(outputs)]
             if i_new == 0:
                 step_scores = [[o] for o in outputs]
                 step_tokens = [[t] for t in toks]
@@ -408,6 +426,8 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
                "step_s": step_times, "tokens_last_pass": tokens, "stats": runner.stats,
                "hbm_cache_kept_shards": len(getattr(runner.prefetcher, "_sticky", ())),
                "prefix_kv_cache": runner.prefix_cache is not None}
+    sampling = SamplingParams.from_args(args)
+    metrics["sampling"] = sampling.as_dict() if sampling is not None else {"do_sample": False}
     if device.type == "cuda":
         metrics["peak_hbm_bytes"] = torch.cuda.max_memory_allocated(device)
     if comm.rank == 0:

@@ -46,6 +46,8 @@ from .runtime.activations import ActivationStore, ActRing
 from .runtime.batch import Q_BLOCK, Q_BLOCK_MHA, PackedBatch, pack_prompts, split_microbatches
 from .runtime.prefetch import ShardPrefetcher
 from .runtime.weights import LayerSource
+from .sampling import MAX_VOCAB
+from .sampling import draws as sample_draws
 from .utils import trace
 from .utils.tokenizer import TokenizedPrompt, tokenize_prompts
 
@@ -79,7 +81,8 @@ class ShardedRunner:
                  prefix_kv_cache: bool = False, prefix_cache_entries: int = 8, suffix_kv_cache: bool = False,
                  prune_last_layer: bool = True, pipeline_stages: str = "round_robin",
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
-                 exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token"):
+                 exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token",
+                 sampling=None):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
         if score_mode not in ("next_token", "loglik"):
@@ -96,6 +99,17 @@ class ShardedRunner:
                               "model parallel (several GPUs without --data_parallel)")):
                 if on:
                     raise ValueError(f"--score_mode loglik does not combine with {flag}")
+        # sampled generation (sampling.SamplingParams; None: greedy): every next token is drawn by
+        # _pick_rows from the row's fp16 probabilities, as a function of (row, seed, prompt index,
+        # suffix index, step) only
+        if sampling is not None and self.loglik:
+            raise ValueError("--do_sample does not combine with --score_mode loglik")
+        if sampling is not None and cfg.vocab_size >= MAX_VOCAB:
+            raise ValueError(f"--do_sample supports vocabularies below {MAX_VOCAB}, got {cfg.vocab_size}")
+        self.sampling = sampling
+        self.sample_step = 0               # the generation step of the next call (api.generation_loop)
+        self.prompt_base = 0               # index in the prompt file of the next call's first prompt
+        self._sample_table: Optional[torch.Tensor] = None
         # last call's per-token log-probabilities (loglik): per prompt a list of n_s float32 arrays
         self.last_token_logprobs: List[Optional[List[np.ndarray]]] = []
         self.sliding_window_mode = sliding_window_mode
@@ -262,7 +276,10 @@ class ShardedRunner:
         self._graphs = None
         self._decode_graphs = None
         self._spec: Optional[dict] = None     # an enqueued speculative generation step
-        self.last_tokens: List[Optional[np.ndarray]] = []   # last call's greedy token per suffix
+        self.last_tokens: List[Optional[np.ndarray]] = []   # last call's greedy (or sampled) token per suffix
+        if self.sampling is not None:
+            # the weight table, uploaded once (every weight is <= 2^30: the uint32 values as int32)
+            self._sample_table = torch.from_numpy(self.sampling.table().view(np.int32)).to(self.dev)
         if self.cuda and not self.hip_graphs:
             from .models.llama import Workspace
             self.ctx.ws = Workspace(self.dev, self.act_dtype)   # fixed scratch buffers (VRAM plan)
@@ -1113,15 +1130,34 @@ class ShardedRunner:
         }
         return outputs
 
-    def _enqueue_graphed(self, batches, run):
-        """Replay every micro-batch (``run(batch, index) -> probs``), its row argmax and the D2H
-        of both into pooled pinned buffers, all on the current stream -> (pending, argmax tensors,
-        decoder FLOPs)."""
+    def _pick_rows(self, batch: PackedBatch, probs: torch.Tensor, step: int) -> torch.Tensor:
+        """[rows] int32 on the device: the next token of every suffix of ``batch``.  Greedy: the
+        row argmax.  Sampling: ``ops.sample_rows`` with the batch's draws for generation step
+        ``step`` (they depend on no data: a small pinned H2D on the current stream, no
+        synchronisation)."""
+        if self.sampling is None:
+            return self.ops.argmax_rows(probs)
+        d = sample_draws(self.sampling.seed, [self.prompt_base + int(p) for p in batch.prompt_ids],
+                         batch.n_suffix, step)
+        host = torch.from_numpy(d.view(np.int64))
+        if self.cuda:
+            # (a pinned tensor of the caching host allocator: not reused before the copy ran)
+            pinned = torch.empty(host.shape, dtype=torch.int64, pin_memory=True)
+            pinned.copy_(host)
+            host = pinned.to(self.dev, non_blocking=True)
+        return self.ops.sample_rows(probs, self._sample_table, host, self.sampling.top_k, self.sampling.P)
+
+    def _enqueue_graphed(self, batches, run, step: Optional[int] = None):
+        """Replay every micro-batch (``run(batch, index) -> probs``), its row argmax (sampling: the
+        tokens drawn for generation step ``step``, default this call's) and the D2H of both into
+        pooled pinned buffers, all on the current stream -> (pending, token tensors, decoder
+        FLOPs)."""
+        step = self.sample_step if step is None else step
         store = self._get_store()
         pending, ams, flops = [], [], 0.0
         for i, batch in enumerate(batches):
             probs = run(batch, i)
-            am = self.ops.argmax_rows(probs)
+            am = self._pick_rows(batch, probs, step)
             nbytes = probs.numel() * probs.element_size()
             pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])
             host = pool_buf[:nbytes].view(probs.dtype).view(probs.shape)
@@ -1186,7 +1222,9 @@ class ShardedRunner:
             graphs = self._decode_graphs
             pe, self.ctx.prefix_entry = self.ctx.prefix_entry, entry     # (a capture's eager forward reads it)
             try:
-                pending, ams2, flops = self._enqueue_graphed(sb, lambda b, i: graphs.run(b, entry, ids_dev=ams[i]))
+                # (sampling: the speculative step is generation step sample_step + 1)
+                pending, ams2, flops = self._enqueue_graphed(sb, lambda b, i: graphs.run(b, entry, ids_dev=ams[i]),
+                                                             step=self.sample_step + 1)
             finally:
                 self.ctx.prefix_entry = pe
             done = torch.cuda.Event()
@@ -1358,7 +1396,7 @@ class ShardedRunner:
         if self.loglik:
             am = None                 # probs: the fp32 [n_pairs, 2] head state, copied as it is
         else:
-            am = self.ops.argmax_rows(probs) if hasattr(self.ops, "argmax_rows") else None
+            am = self._pick_rows(batch, probs, self.sample_step) if hasattr(self.ops, "argmax_rows") else None
         if not self.cuda:
             return batch, probs.detach().to(torch.float32 if self.loglik else torch.float16).cpu(), None, None, am
         store = self._get_store()

@@ -519,6 +519,34 @@ class HipOps:
                                     out.data_ptr(), _stream()), "fls_argmax_rows")
         return out
 
+    def sample_rows(self, probs, table_dev, draws_dev, top_k: int, P: int):
+        """[rows] int32: the sampled token of each row of fp16 probabilities (sampling.py holds the
+        definition).  ``table_dev``: the 0x3C01 uint32 weights as an int32 CUDA vector (every
+        weight is <= 2^30); ``draws_dev``: one uint64 draw per row as an int64 CUDA vector;
+        ``P = round(top_p * 65536)``."""
+        from ..sampling import MAX_VOCAB, TABLE_SIZE
+        _f16(probs, "probs")
+        rows, V = probs.shape
+        if V >= MAX_VOCAB:
+            raise ValueError(f"sampling supports vocabularies below {MAX_VOCAB}, got {V}")
+        if probs.stride(1) != 1 or probs.stride(0) < V:
+            raise TypeError("probs must have unit column stride and a row stride >= V")
+        if (table_dev.dtype != torch.int32 or not table_dev.is_cuda or not table_dev.is_contiguous()
+                or table_dev.numel() != TABLE_SIZE):
+            raise TypeError(f"table must be a contiguous int32 CUDA vector of {TABLE_SIZE} entries")
+        if (draws_dev.dtype != torch.int64 or not draws_dev.is_cuda or not draws_dev.is_contiguous()
+                or draws_dev.numel() != rows):
+            raise TypeError(f"draws must be a contiguous int64 CUDA vector of {rows} entries")
+        if table_dev.device != probs.device or draws_dev.device != probs.device:
+            raise TypeError("probs, table and draws must be on one device")
+        if int(top_k) < 0 or not 1 <= int(P) <= 65536:
+            raise ValueError(f"top_k >= 0 and P in [1, 65536] expected, got {top_k} and {P}")
+        out = torch.empty(rows, dtype=torch.int32, device=probs.device)
+        _chk(self.k.fls_sample_rows(probs.data_ptr(), probs.stride(0), rows, V, table_dev.data_ptr(),
+                                    draws_dev.data_ptr(), int(top_k), int(P), out.data_ptr(), _stream()),
+             "fls_sample_rows")
+        return out
+
     def lm_head_softmax(self, h, w, logits_scaling: float = 1.0):
         return self.softmax(self.linear(h, w), logits_scaling)
 

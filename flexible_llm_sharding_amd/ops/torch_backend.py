@@ -9,6 +9,7 @@ what the HIP kernels consume, so this backend is a drop-in oracle for them.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -239,6 +240,16 @@ class TorchOps:
 
     def argmax_rows(self, probs: torch.Tensor) -> torch.Tensor:
         return probs.float().argmax(-1).to(torch.int32)
+
+    def sample_rows(self, probs: torch.Tensor, table: torch.Tensor, draws: torch.Tensor, top_k: int,
+                    P: int) -> torch.Tensor:
+        """HipOps.sample_rows through the host sampler (sampling.sample_tokens: the same tokens).
+        ``table``: int32 weights, ``draws``: the uint64 draws as int64."""
+        from ..sampling import sample_tokens
+        p16 = probs.detach().to(torch.float16).cpu().numpy()
+        tok = sample_tokens(p16, table.cpu().numpy().view(np.uint32), int(top_k), int(P),
+                            draws.cpu().numpy().view(np.uint64))
+        return torch.from_numpy(tok.astype(np.int32)).to(probs.device)
 
     def softmax(self, logits: torch.Tensor, logits_scaling: float = 1.0) -> torch.Tensor:
         if logits_scaling != 1.0:                            # Granite: logits / logits_scaling

@@ -62,6 +62,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "one); --output_file then holds the per-token log-probabilities.  Not with --num_gen_token "
                         "> 1, --hip_graphs, --prefix_kv_cache / --suffix_kv_cache true, --resume_dir or model "
                         "parallel")
+    p.add_argument("--do_sample", type=str2bool, nargs="?", const=True, default=False,
+                   help="draw every generated token from the next-token distribution instead of taking its "
+                        "argmax (temperature, then top-k, then top-p; integer-exact, so device and host draw the "
+                        "same token: sampling.py).  The scores are unchanged; a run is a function of its prompts "
+                        "and --seed.  Not with --score_mode loglik")
+    p.add_argument("--temperature", type=float, default=1.0,
+                   help="with --do_sample: sample from p^(1/T) renormalised (softmax(logits / T) over the tokens "
+                        "whose fp16 probability is non-zero); > 0")
+    p.add_argument("--top_k", type=int, default=0, help="with --do_sample: keep the k most probable tokens (0: off)")
+    p.add_argument("--top_p", type=float, default=1.0,
+                   help="with --do_sample: keep the shortest most-probable prefix holding this share of the "
+                        "(temperature-weighted, top-k truncated) mass; in (0, 1]")
+    p.add_argument("--seed", type=int, default=0, help="with --do_sample: the seed of every draw")
     p.add_argument("--hip_graphs", type=str2bool, nargs="?", const=True, default=False,
                    help="with --resident: capture each micro-batch's whole forward as one HIP graph and "
                         "replay it (shape-bucketed; removes per-op host dispatch for small batches)")
@@ -146,7 +159,23 @@ def check_score_mode(args) -> None:
             raise ValueError(f"--score_mode loglik does not combine with {flag}")
 
 
+def check_sampling(args) -> None:
+    """The sampling flags: values in range, no sampling parameter without ``--do_sample``, no
+    sampling inside ``--score_mode loglik``; a ``ValueError`` names the flag."""
+    from ..sampling import check_sampling_values
+    t, k, p = getattr(args, "temperature", 1.0), getattr(args, "top_k", 0), getattr(args, "top_p", 1.0)
+    check_sampling_values(t, k, p)
+    if not getattr(args, "do_sample", False):
+        for v, default, flag in ((t, 1.0, "--temperature"), (k, 0, "--top_k"), (p, 1.0, "--top_p")):
+            if v != default:
+                raise ValueError(f"{flag} needs --do_sample (generation is greedy without it)")
+        return
+    if getattr(args, "score_mode", "next_token") == "loglik":
+        raise ValueError("--do_sample does not combine with --score_mode loglik")
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     check_score_mode(args)
+    check_sampling(args)
     return args
