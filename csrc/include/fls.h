@@ -166,6 +166,15 @@ int fls_logprob_rows(const void* logits, int ld, int rows, int V, const int* tar
 // Integer-exact (csrc/kernels/sampling.hip); top_k = 1 or P = 1 gives fls_argmax_rows' token.
 int fls_sample_rows(const void* probs, int ld, int rows, int V, const uint32_t* table, const uint64_t* draws,
                     int top_k, int P, int* out, fls_stream_t s);
+// ids[r, 0..K) / vals[r, 0..K) = the K best entries of row r of fp16 probabilities (row stride ld),
+// ranked by (key descending, index ascending); the key of a bit pattern b is b if b <= 0x3C00
+// (0 <= p <= 1), else 0 (negative, NaN and > 1 rank with the zeros), and vals holds the keys.
+// picked ([rows] int32, with picked_vals [rows] fp16; both null or both given): picked_vals[r] =
+// the key of entry picked[r]; an id outside [0, V) is never read and gives 0.
+// Integer-exact (csrc/kernels/topk.hip); ids[r, 0] is fls_argmax_rows' token of a valid row.
+// hipErrorInvalidValue for V <= 0, ld < V, K < 1, K > V, K > 1024; rows <= 0 does nothing.
+int fls_topk_rows(const void* probs, int ld, int rows, int V, int K, int* ids, void* vals, const int* picked,
+                  void* picked_vals, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0

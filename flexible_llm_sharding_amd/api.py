@@ -34,7 +34,7 @@ from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
 from .sampling import SamplingParams, draws as sample_draws, sample_tokens
-from .utils.cli import check_sampling, check_score_mode, parse_args
+from .utils.cli import check_sampling, check_score_mode, check_top_k, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -184,6 +184,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     from .models.layout import layer_kind
     check_score_mode(args)             # (args built without parse_args too)
     check_sampling(args)
+    check_top_k(args, comm.world)
     if getattr(args, "score_mode", "next_token") == "loglik" and comm.world > 1 and not args.data_parallel:
         raise ValueError("--score_mode loglik does not combine with model parallel: pass --data_parallel")
     pkv = resolve_prefix_kv_cache(args)
@@ -242,7 +243,8 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          max_vram_gb=getattr(args, "max_vram_gb", None),
                          # one rank draws the tokens on the device; several ranks: rank 0 draws the
                          # same tokens on the host from the gathered scores (generation_loop)
-                         sampling=SamplingParams.from_args(args) if comm.world == 1 else None)
+                         sampling=SamplingParams.from_args(args) if comm.world == 1 else None,
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0))
 
 
 def load_model_meta(args):
@@ -288,7 +290,12 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
         return sum((o for o, _ in allv), [])
     if comm.world == 1:
         return outs
-    allv = comm.gather_scores(outs, dst=0)
+    if getattr(runner, "score_top_k", 0):
+        # K (id, probability) pairs per row: gathered as objects (gather_scores packs fp16 and
+        # cannot carry the ids)
+        allv = comm.gather_object(outs, dst=0)
+    else:
+        allv = comm.gather_scores(outs, dst=0)
     if comm.rank != 0:
         return []
     if args.data_parallel:
@@ -300,14 +307,20 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
     raise RuntimeError("no rank produced scores")
 
 
-def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, step_times: Optional[list] = None):
+def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, step_times: Optional[list] = None,
+                    token_record: Optional[dict] = None):
     """main.py:63-90 — greedy extension of every suffix, one full pass per step (the prefix K/V
     cache and the HBM weight cache, on by default for repeated passes, make the later passes
     cheaper; the scores are the same).  ``step_times`` collects each step's wall time.
     ``--do_sample``: the appended token is drawn from the step's scores instead (sampling.py), on
-    the device where the runner holds every prompt, else here on rank 0: the same tokens."""
+    the device where the runner holds every prompt, else here on rank 0: the same tokens.
+    ``--score_top_k``: every step's output is a ``TOPK_DTYPE`` [n_s, 1, K] array per prompt; rank 0
+    fills ``token_record`` with ``token_ids`` (int64 [n_s, steps] per prompt, the appended
+    tokens) and ``token_probs`` (float16, their probabilities)."""
     input_prompts = copy.deepcopy(list(original_prompts))
     sampling = SamplingParams.from_args(args)
+    top_k = int(getattr(runner, "score_top_k", 0) or 0)
+    step_probs: List[List[np.ndarray]] = []          # score_top_k: per prompt, every step's [n_s, 1] fp16
     table = sampling.table() if sampling is not None and comm.rank == 0 else None
     # per prompt: every step's [n_s, 1, V] scores and argmax tokens.  The reference concatenates the
     # scores each step and takes the argmax over all of them (main.py:83-88); the argmax of the
@@ -345,8 +358,20 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
             prof.disable()
             prof.dump_stats(f"gen_profile.{i_new}")
         if comm.rank == 0:
+            if top_k:
+                if dev_tok is not None:
+                    probs_t = list(runner.last_token_probs)
+                elif sampling is not None:
+                    raise RuntimeError("--score_top_k with --do_sample needs the tokens drawn on the device")
+                else:
+                    # the greedy token is the first ranked entry (several ranks or batches)
+                    probs_t = [o["p"][:, :, 0] for o in outputs]
+                for pi, pt in enumerate(probs_t):
+                    step_probs.append([pt]) if i_new == 0 else step_probs[pi].append(pt)
             if dev_tok is not None:
                 toks = dev_tok
+            elif top_k:
+                toks = [o["id"][:, :, 0].astype(np.int64) for o in outputs]
             elif sampling is None:
                 toks = [greedy_tokens(o) for o in outputs]
             else:
@@ -374,6 +399,9 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
         if getattr(args, "verbose", False) and comm.rank == 0:
             print(f"step {i_new}: {time.perf_counter() - t_step:.3f}s", flush=True)
     output_scores = [ss[0] if len(ss) == 1 else np.concatenate(ss, axis=1) for ss in step_scores]
+    if top_k and token_record is not None:
+        token_record["token_ids"] = [np.concatenate(ts, axis=1).astype(np.int64) for ts in step_tokens]
+        token_record["token_probs"] = [np.concatenate(ps, axis=1).astype(np.float16) for ps in step_probs]
     return output_scores, input_prompts
 
 
@@ -418,7 +446,15 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
         updated = copy.deepcopy(list(original))
         step_times.append(time.perf_counter() - t1)
     else:
-        scores, updated = generation_loop(args, runner, comm, tok, original, step_times)
+        rec: dict = {}
+        scores, updated = generation_loop(args, runner, comm, tok, original, step_times, token_record=rec)
+        if getattr(runner, "score_top_k", 0):
+            # compact scores: the K best (id, probability) pairs of every suffix and step, and the
+            # appended tokens with their probabilities
+            scores = {"k": runner.score_top_k,
+                      "top_ids": [np.ascontiguousarray(o["id"]) for o in scores],
+                      "top_probs": [np.ascontiguousarray(o["p"]) for o in scores],
+                      "token_ids": rec.get("token_ids", []), "token_probs": rec.get("token_probs", [])}
     t_run = time.perf_counter() - t1
     tokens = comm.all_reduce_sum(runner.stats.get("tokens", 0.0)) if not (
         comm.world > 1 and not args.data_parallel) else runner.stats.get("tokens", 0.0)
@@ -428,6 +464,8 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
                "prefix_kv_cache": runner.prefix_cache is not None}
     sampling = SamplingParams.from_args(args)
     metrics["sampling"] = sampling.as_dict() if sampling is not None else {"do_sample": False}
+    metrics["score_top_k"] = int(getattr(runner, "score_top_k", 0))
+    metrics["score_d2h_bytes_last_pass"] = int(getattr(runner, "score_d2h_bytes", 0))
     if device.type == "cuda":
         metrics["peak_hbm_bytes"] = torch.cuda.max_memory_allocated(device)
     if comm.rank == 0:

@@ -48,6 +48,7 @@ from .runtime.prefetch import ShardPrefetcher
 from .runtime.weights import LayerSource
 from .sampling import MAX_VOCAB
 from .sampling import draws as sample_draws
+from .topk import TOPK_DTYPE, check_k
 from .utils import trace
 from .utils.tokenizer import TokenizedPrompt, tokenize_prompts
 
@@ -82,7 +83,7 @@ class ShardedRunner:
                  prune_last_layer: bool = True, pipeline_stages: str = "round_robin",
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
                  exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token",
-                 sampling=None):
+                 sampling=None, score_top_k: int = 0):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
         if score_mode not in ("next_token", "loglik"):
@@ -107,6 +108,16 @@ class ShardedRunner:
         if sampling is not None and cfg.vocab_size >= MAX_VOCAB:
             raise ValueError(f"--do_sample supports vocabularies below {MAX_VOCAB}, got {cfg.vocab_size}")
         self.sampling = sampling
+        # compact scores (topk.py; 0: off): per scored row the K best (token id, probability) pairs
+        # and the chosen token's probability leave the device instead of the [rows, V] scores
+        if score_top_k:
+            if self.loglik:
+                raise ValueError("--score_top_k does not combine with --score_mode loglik")
+            score_top_k = check_k(score_top_k, cfg.vocab_size)
+        self.score_top_k = int(score_top_k)
+        # last call's probability of each suffix's chosen token (score_top_k): fp16 [n_s, 1] per prompt
+        self.last_token_probs: List[Optional[np.ndarray]] = []
+        self.score_d2h_bytes = 0           # bytes of scores the last call copied to the host
         self.sample_step = 0               # the generation step of the next call (api.generation_loop)
         self.prompt_base = 0               # index in the prompt file of the next call's first prompt
         self._sample_table: Optional[torch.Tensor] = None
@@ -330,7 +341,9 @@ class ShardedRunner:
     def __call__(self, prompts) -> List[np.ndarray]:
         """Reference API: list of (prefix, suffixes) -> list of [n_s, 1, V] fp16 arrays.
         ``score_mode="loglik"``: list of [n_s, 3] float32 arrays (log p(suffix | prefix), its token
-        count, 1.0 if every token is the greedy one), per-token values in ``last_token_logprobs``."""
+        count, 1.0 if every token is the greedy one), per-token values in ``last_token_logprobs``.
+        ``score_top_k=K``: list of ``TOPK_DTYPE`` [n_s, 1, K] arrays (the K best (id, probability)
+        pairs in rank order, topk.py), the chosen tokens' probabilities in ``last_token_probs``."""
         if self.my_shards and prompts and not self.resume_dir and not self.hip_graphs:
             # the first shards' weights do not depend on the prompts: their H2D overlaps tokenization
             if self._h2d0 is None:
@@ -939,6 +952,8 @@ class ShardedRunner:
             px.inbox.end_call()
             rx_stats = {f"rx_{k}": float(v) for k, v in px.inbox.stats.items()}
         self.last_tokens = [None] * len(px.tps)
+        self.last_token_probs = [None] * len(px.tps)
+        self.score_d2h_bytes = 0
         for batch, host, ev, pool_buf, am in px.out_pending:
             self._collect(batch, host.numpy(), am, px.outputs)
             if pool_buf is not None:
@@ -1158,13 +1173,18 @@ class ShardedRunner:
         for i, batch in enumerate(batches):
             probs = run(batch, i)
             am = self._pick_rows(batch, probs, step)
-            nbytes = probs.numel() * probs.element_size()
-            pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])
-            host = pool_buf[:nbytes].view(probs.dtype).view(probs.shape)
-            host_am = pool_buf[nbytes:nbytes + 4 * probs.shape[0]].view(torch.int32)
-            host.copy_(probs, non_blocking=True)     # same stream: ordered before the next replay
-            host_am.copy_(am, non_blocking=True)
-            pending.append((batch, host, pool_buf, host_am))
+            if self.score_top_k:
+                # the K best entries and the tokens' probabilities instead of the rows themselves
+                host, pool_buf = self._topk_to_host(probs, am, None)
+                pending.append((batch, host, pool_buf, None))
+            else:
+                nbytes = probs.numel() * probs.element_size()
+                pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])
+                host = pool_buf[:nbytes].view(probs.dtype).view(probs.shape)
+                host_am = pool_buf[nbytes:nbytes + 4 * probs.shape[0]].view(torch.int32)
+                host.copy_(probs, non_blocking=True)     # same stream: ordered before the next replay
+                host_am.copy_(am, non_blocking=True)
+                pending.append((batch, host, pool_buf, host_am))
             ams.append(am)
             # every unpruned decoder layer has the same count: one evaluation each way (80 per step
             # cost 3.4 ms of host time, on the path that must stay under a generation step's GPU time)
@@ -1178,6 +1198,8 @@ class ShardedRunner:
     def _collect_graphed(self, pending, outputs, n_prompts: int) -> None:
         store = self._get_store()
         self.last_tokens = [None] * n_prompts
+        self.last_token_probs = [None] * n_prompts
+        self.score_d2h_bytes = 0
         for batch, host, pool_buf, host_am in pending:
             self._collect(batch, host.numpy(), host_am, outputs)
             store.recycle_host(pool_buf)
@@ -1359,8 +1381,11 @@ class ShardedRunner:
     def _collect(self, batch: PackedBatch, probs: np.ndarray, am, outputs) -> None:
         """Host scores of a finished micro-batch into ``outputs`` (prompt order) and its greedy
         tokens into ``self.last_tokens`` (``am``: the rows' argmax, computed on the device)."""
+        self.score_d2h_bytes += probs.nbytes + (4 * am.numel() if am is not None else 0)
         if self.loglik:
             return self._collect_loglik(batch, probs, outputs)
+        if self.score_top_k:
+            return self._collect_topk(batch, probs, outputs)
         am = am.numpy() if am is not None else None
         r = 0
         for j, pid in enumerate(batch.prompt_ids):
@@ -1390,9 +1415,78 @@ class ShardedRunner:
             outputs[pid] = out
             self.last_token_logprobs[pid] = per_tok
 
+    # ------------------------------------------------- compact scores (score_top_k)
+    def _topk_offsets(self, rows: int):
+        """Byte offsets of a micro-batch's compact scores in one host buffer: ids int32 [rows, K],
+        tokens int32 [rows], probabilities fp16 [rows, K], token probabilities fp16 [rows] (the
+        int32 parts first, so every view stays aligned) -> (tokens, probabilities, token
+        probabilities, total)."""
+        K = self.score_top_k
+        o_tok = 4 * rows * K
+        o_vals = o_tok + 4 * rows
+        o_pv = o_vals + 2 * rows * K
+        return o_tok, o_vals, o_pv, o_pv + 2 * rows
+
+    def _topk_to_host(self, probs: torch.Tensor, am: torch.Tensor, stream):
+        """``ops.topk_rows`` of a micro-batch's probabilities and its chosen tokens ``am`` on the
+        current stream (a plain launch: right behind a graph replay too), then the D2H of the four
+        small results into one pooled pinned buffer on ``stream`` (None: the current stream) ->
+        (the buffer's used bytes, the pooled buffer).  Without a GPU: (a host byte tensor, None)."""
+        rows, K = probs.shape[0], self.score_top_k
+        ids, vals, pv = self.ops.topk_rows(probs, K, picked=am)
+        parts = (ids, am, vals, pv)
+        if not self.cuda:
+            return torch.cat([p.detach().cpu().contiguous().reshape(-1).view(torch.uint8) for p in parts]), None
+        o_tok, o_vals, o_pv, total = self._topk_offsets(rows)
+        pool_buf = self._get_store().host_buffer(total)
+        views = (pool_buf[:o_tok].view(torch.int32).view(rows, K), pool_buf[o_tok:o_vals].view(torch.int32),
+                 pool_buf[o_vals:o_pv].view(torch.float16).view(rows, K), pool_buf[o_pv:total].view(torch.float16))
+        if stream is None:
+            for h, d in zip(views, parts):
+                h.copy_(d, non_blocking=True)        # same stream: ordered before the next replay
+        else:
+            stream.wait_stream(torch.cuda.current_stream(self.dev))
+            with torch.cuda.stream(stream):
+                for h, d in zip(views, parts):
+                    h.copy_(d, non_blocking=True)
+                    d.record_stream(stream)
+        return pool_buf[:total], pool_buf
+
+    def _collect_topk(self, batch: PackedBatch, buf: np.ndarray, outputs) -> None:
+        """The host bytes of a finished micro-batch (``_topk_offsets``) split back into prompts:
+        per prompt a ``TOPK_DTYPE`` [n_s, 1, K] array into ``outputs``, the chosen tokens into
+        ``self.last_tokens`` and their probabilities into ``self.last_token_probs``."""
+        K = self.score_top_k
+        rows = int(sum(batch.n_suffix))
+        o_tok, o_vals, o_pv, total = self._topk_offsets(rows)
+        assert buf.dtype == np.uint8 and buf.size == total, (buf.dtype, buf.size, total)
+        ids = buf[:o_tok].view(np.int32).reshape(rows, K)
+        tok = buf[o_tok:o_vals].view(np.int32)
+        vals = buf[o_vals:o_pv].view(np.float16).reshape(rows, K)
+        pv = buf[o_pv:total].view(np.float16)
+        r = 0
+        for j, pid in enumerate(batch.prompt_ids):
+            ns = batch.n_suffix[j]
+            out = np.empty((ns, 1, K), dtype=TOPK_DTYPE)
+            out["id"][:, 0, :] = ids[r:r + ns]
+            out["p"][:, 0, :] = vals[r:r + ns]
+            outputs[pid] = out
+            self.last_tokens[pid] = tok[r:r + ns].astype(np.int64).reshape(ns, 1)
+            self.last_token_probs[pid] = pv[r:r + ns].copy().reshape(ns, 1)
+            r += ns
+
     def _start_output_copy(self, batch: PackedBatch, probs: torch.Tensor):
         """D2H of a micro-batch's probabilities and of their row argmax (the greedy token of
-        each suffix: api.generation_loop needs no host pass over the [n_s, V] scores)."""
+        each suffix: api.generation_loop needs no host pass over the [n_s, V] scores).
+        ``score_top_k``: of the K best entries and the tokens' probabilities instead."""
+        if self.score_top_k:
+            am = self._pick_rows(batch, probs, self.sample_step)
+            host, pool_buf = self._topk_to_host(probs, am, self.d2h_stream)
+            if not self.cuda:
+                return batch, host, None, None, None
+            ev = torch.cuda.Event()
+            ev.record(self.d2h_stream)
+            return batch, host, ev, pool_buf, None
         if self.loglik:
             am = None                 # probs: the fp32 [n_pairs, 2] head state, copied as it is
         else:

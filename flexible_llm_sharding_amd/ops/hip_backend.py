@@ -547,6 +547,34 @@ class HipOps:
              "fls_sample_rows")
         return out
 
+    def topk_rows(self, probs, K: int, picked=None):
+        """(ids int32 [rows, K], vals fp16 [rows, K], picked_vals fp16 [rows] | None): the K best
+        entries of each row of fp16 probabilities in rank order (topk.py holds the definition), and
+        the clamped probability of entry ``picked[r]`` (an int32 CUDA vector) of every row."""
+        from ..topk import MAX_K
+        _f16(probs, "probs")
+        if probs.dim() != 2:
+            raise TypeError("probs must be a [rows, V] tensor")
+        rows, V = probs.shape
+        if probs.stride(1) != 1 or probs.stride(0) < V:
+            raise TypeError("probs must have unit column stride and a row stride >= V")
+        if picked is not None:
+            if (picked.dtype != torch.int32 or not picked.is_cuda or not picked.is_contiguous()
+                    or picked.numel() != rows):
+                raise TypeError(f"picked must be a contiguous int32 CUDA vector of {rows} entries")
+            if picked.device != probs.device:
+                raise TypeError("probs and picked must be on one device")
+        if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= min(V, MAX_K):
+            raise ValueError(f"K in 1..min(V, {MAX_K}) expected, got {K} at V = {V}")
+        K = int(K)
+        ids = torch.empty(rows, K, dtype=torch.int32, device=probs.device)
+        vals = torch.empty(rows, K, dtype=torch.float16, device=probs.device)
+        pv = torch.empty(rows, dtype=torch.float16, device=probs.device) if picked is not None else None
+        _chk(self.k.fls_topk_rows(probs.data_ptr(), probs.stride(0), rows, V, K, ids.data_ptr(), vals.data_ptr(),
+                                  picked.data_ptr() if picked is not None else None,
+                                  pv.data_ptr() if pv is not None else None, _stream()), "fls_topk_rows")
+        return ids, vals, pv
+
     def lm_head_softmax(self, h, w, logits_scaling: float = 1.0):
         return self.softmax(self.linear(h, w), logits_scaling)
 

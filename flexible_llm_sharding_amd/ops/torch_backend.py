@@ -251,6 +251,23 @@ class TorchOps:
                             draws.cpu().numpy().view(np.uint64))
         return torch.from_numpy(tok.astype(np.int32)).to(probs.device)
 
+    def topk_rows(self, probs: torch.Tensor, K: int, picked: Optional[torch.Tensor] = None):
+        """HipOps.topk_rows through the host implementation (topk.topk_rows: the same entries)."""
+        from ..topk import MAX_K, picked_keys, topk_rows
+        if probs.dim() != 2:
+            raise TypeError("probs must be a [rows, V] tensor")
+        rows, V = probs.shape
+        if picked is not None and (picked.dtype != torch.int32 or picked.numel() != rows):
+            raise TypeError(f"picked must be an int32 vector of {rows} entries")
+        if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= min(V, MAX_K):
+            raise ValueError(f"K in 1..min(V, {MAX_K}) expected, got {K} at V = {V}")
+        p16 = probs.detach().to(torch.float16).cpu().numpy()
+        ids, vals = topk_rows(p16, int(K))
+        pv = None
+        if picked is not None:
+            pv = torch.from_numpy(picked_keys(p16, picked.cpu().numpy()).view(np.float16)).to(probs.device)
+        return (torch.from_numpy(ids).to(probs.device), torch.from_numpy(vals.view(np.float16)).to(probs.device), pv)
+
     def softmax(self, logits: torch.Tensor, logits_scaling: float = 1.0) -> torch.Tensor:
         if logits_scaling != 1.0:                            # Granite: logits / logits_scaling
             logits = logits / logits_scaling

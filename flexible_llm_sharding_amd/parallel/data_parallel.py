@@ -361,7 +361,8 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                          suffix_kv_cache=_suffix_kv(args, comm), exact_reuse=getattr(args, "exact_reuse", True),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          score_mode=getattr(args, "score_mode", "next_token"),
-                         max_vram_gb=getattr(args, "max_vram_gb", None))
+                         max_vram_gb=getattr(args, "max_vram_gb", None),
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0))
 
 
 def _suffix_kv(args, comm: Comm) -> bool:

@@ -75,6 +75,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --do_sample: keep the shortest most-probable prefix holding this share of the "
                         "(temperature-weighted, top-k truncated) mass; in (0, 1]")
     p.add_argument("--seed", type=int, default=0, help="with --do_sample: the seed of every draw")
+    p.add_argument("--score_top_k", type=int, default=0,
+                   help="with --score_mode next_token: instead of the whole [n_s, steps, V] distribution, return "
+                        "per suffix and step the K most probable (token id, fp16 probability) pairs, selected on "
+                        "the device in rank order (probability descending, id ascending; topk.py), and the id and "
+                        "probability of the appended token; the [rows, V] scores are never copied to the host.  "
+                        "0 (default): off; at most 1024 and the vocabulary size.  Tokens, probabilities and "
+                        "updated prompts are those of the run without the flag.  Not with --score_mode loglik, nor "
+                        "with --do_sample on several GPUs or with --num_batch > 1")
     p.add_argument("--hip_graphs", type=str2bool, nargs="?", const=True, default=False,
                    help="with --resident: capture each micro-batch's whole forward as one HIP graph and "
                         "replay it (shape-bucketed; removes per-op host dispatch for small batches)")
@@ -174,8 +182,28 @@ def check_sampling(args) -> None:
         raise ValueError("--do_sample does not combine with --score_mode loglik")
 
 
+def check_top_k(args, world: int = 1) -> None:
+    """``--score_top_k``: 0 (off) or 1..1024, in ``--score_mode next_token`` only, and not where
+    sampled tokens are drawn on the host from the full rows (``--do_sample`` with several ranks
+    or ``--num_batch > 1``); a ``ValueError`` names the flag.  The vocabulary bound is checked
+    where the runner is built."""
+    from ..topk import check_k
+    k = getattr(args, "score_top_k", 0)
+    if k == 0 and not isinstance(k, bool):
+        return
+    if isinstance(k, bool) or int(k) != k or k < 0:
+        raise ValueError(f"--score_top_k must be an integer >= 0, got {k!r}")
+    check_k(k)
+    if getattr(args, "score_mode", "next_token") == "loglik":
+        raise ValueError("--score_top_k does not combine with --score_mode loglik")
+    if getattr(args, "do_sample", False) and (world > 1 or getattr(args, "num_batch", 1) > 1):
+        raise ValueError("--score_top_k does not combine with --do_sample on several GPUs or with --num_batch > 1: "
+                         "the host sampler needs the full rows")
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     check_score_mode(args)
     check_sampling(args)
+    check_top_k(args)
     return args
