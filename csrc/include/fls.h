@@ -175,6 +175,15 @@ int fls_sample_rows(const void* probs, int ld, int rows, int V, const uint32_t* 
 // hipErrorInvalidValue for V <= 0, ld < V, K < 1, K > V, K > 1024; rows <= 0 does nothing.
 int fls_topk_rows(const void* probs, int ld, int rows, int V, int K, int* ids, void* vals, const int* picked,
                   void* picked_vals, fls_stream_t s);
+// prompt-lookup draft verification (csrc/kernels/lookup.hip).  Suffix i owns rows row_start[i] ..
+// row_start[i + 1] - 1 of the fp16 probabilities (row stride ld; row_start: n_sfx + 1 int32, non-
+// decreasing, within [0, rows]); draft[r] is the draft token scored next to row r, -1 on a suffix's
+// last row.  tok[r] = fls_argmax_rows' token of row r; accept[i] = the number of leading rows of
+// suffix i whose token equals their draft; keep[0 .. n_kept[0]) = rows 0 .. accept[i] of every
+// suffix, in suffix order (keep holds `rows` ints).  Two launches on s, no host synchronisation.
+// hipErrorInvalidValue for rows < 0, n_sfx < 0, V <= 0, ld < V or a missing array.
+int fls_verify_rows(const void* probs, int ld, int rows, int V, const int* row_start, int n_sfx, const int* draft,
+                    int* tok, int* accept, int* keep, int* n_kept, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0

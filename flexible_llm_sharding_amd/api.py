@@ -34,7 +34,7 @@ from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
 from .sampling import SamplingParams, draws as sample_draws, sample_tokens
-from .utils.cli import check_sampling, check_score_mode, check_top_k, parse_args
+from .utils.cli import check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -185,6 +185,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     check_score_mode(args)             # (args built without parse_args too)
     check_sampling(args)
     check_top_k(args, comm.world)
+    check_lookup(args, comm.world)
     if getattr(args, "score_mode", "next_token") == "loglik" and comm.world > 1 and not args.data_parallel:
         raise ValueError("--score_mode loglik does not combine with model parallel: pass --data_parallel")
     pkv = resolve_prefix_kv_cache(args)
@@ -193,7 +194,8 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     if not args.data_parallel and comm.world > 1:
         n_dec = -(-n_dec // comm.world)
     from .runtime.prefix_cache import suffix_growth
-    growth = suffix_growth(getattr(args, "num_gen_token", 1))
+    # (prompt-lookup decoding: a suffix also holds up to D draft tokens)
+    growth = suffix_growth(getattr(args, "num_gen_token", 1) + int(getattr(args, "lookup_decoding", 0) or 0))
     reserve = prefix_kv_bytes(cfg, tok, prompts, n_dec, suffix_kv_cache=skv, growth=growth) if pkv else 0
     if pkv and getattr(args, "max_vram_gb", None) and not host_kv_fits(reserve):
         # host mode (a VRAM cap): the cache's pinned host buffers
@@ -308,7 +310,7 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
 
 
 def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, step_times: Optional[list] = None,
-                    token_record: Optional[dict] = None):
+                    token_record: Optional[dict] = None, drafter=None, lookup_stats: Optional[dict] = None):
     """main.py:63-90 — greedy extension of every suffix, one full pass per step (the prefix K/V
     cache and the HBM weight cache, on by default for repeated passes, make the later passes
     cheaper; the scores are the same).  ``step_times`` collects each step's wall time.
@@ -316,7 +318,13 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
     the device where the runner holds every prompt, else here on rank 0: the same tokens.
     ``--score_top_k``: every step's output is a ``TOPK_DTYPE`` [n_s, 1, K] array per prompt; rank 0
     fills ``token_record`` with ``token_ids`` (int64 [n_s, steps] per prompt, the appended
-    tokens) and ``token_probs`` (float16, their probabilities)."""
+    tokens) and ``token_probs`` (float16, their probabilities).
+    ``--lookup_decoding D``: :func:`lookup_generation_loop` — the same outputs in fewer calls;
+    ``drafter`` (default ``lookup.lookup_draft``) proposes the draft tokens, ``lookup_stats``
+    receives the call and acceptance counts."""
+    if int(getattr(args, "lookup_decoding", 0) or 0) > 0:
+        return lookup_generation_loop(args, runner, comm, tok, original_prompts, step_times, token_record,
+                                      drafter, lookup_stats)
     input_prompts = copy.deepcopy(list(original_prompts))
     sampling = SamplingParams.from_args(args)
     top_k = int(getattr(runner, "score_top_k", 0) or 0)
@@ -405,6 +413,139 @@ def generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence, s
     return output_scores, input_prompts
 
 
+def lookup_generation_loop(args, runner, comm: Comm, tok, original_prompts: Sequence,
+                           step_times: Optional[list] = None, token_record: Optional[dict] = None, drafter=None,
+                           lookup_stats: Optional[dict] = None):
+    """``--lookup_decoding D``: greedy generation in fewer calls, same outputs (lookup.py).
+
+    Every call submits, per suffix with g tokens generated so far, ``s + decode(generated + draft)``
+    (the reference's decode rule, main.py:86-88) with ``draft = drafter(prefix + suffix + generated
+    ids, N, d)[:d]``, d = min(D, num_gen_token - g - 1).  A draft whose text does not re-tokenize to
+    the ids of ``s + decode(generated)`` followed by the draft is dropped for the call (counted).
+    The runner scores each suffix's last ``len(draft) + 1`` rows and keeps the accepted draft
+    positions and the one after them (``ShardedRunner.run_tokenized(drafts=...)``): the suffix
+    gains their greedy tokens and keeps their scores, which — every call being row-exact — are
+    those the one-token-per-call loop computes, as long as decoding and re-tokenizing is
+    prefix-stable (``lookup_retokenized`` counts the suffixes whose next call's ids are not the
+    scored ids plus the gained tokens).  A finished suffix rides along with an empty draft
+    (its scores are discarded); a call without any draft takes the plain path.  One rank, one batch."""
+    from .lookup import DEFAULT_NGRAM, check_lookup_values, lookup_draft
+    from .runtime.prefix_cache import suffix_growth
+    from .utils.tokenizer import TokenizedPrompt
+    D, N = check_lookup_values(getattr(args, "lookup_decoding", 0), getattr(args, "lookup_ngram", DEFAULT_NGRAM))
+    if comm.world != 1 or getattr(args, "num_batch", 1) != 1:
+        raise ValueError("--lookup_decoding runs on one rank with --num_batch 1")
+    drafter = drafter or lookup_draft
+    G = int(args.num_gen_token)
+    top_k = int(getattr(runner, "score_top_k", 0) or 0)
+    n_p = len(original_prompts)
+    gen = [[[] for _ in sfx] for _, sfx in original_prompts]           # generated ids
+    kept_scores = [[[] for _ in sfx] for _, sfx in original_prompts]   # their [rows, V] scores, call by call
+    kept_probs = [[[] for _ in sfx] for _, sfx in original_prompts]    # score_top_k: the tokens' probabilities
+    input_prompts = copy.deepcopy(list(original_prompts))
+    pc = getattr(runner, "prefix_cache", None)
+    if pc is not None:
+        pc.suffix_growth = suffix_growth(G + D)           # a suffix region also holds a call's draft
+    if hasattr(runner, "spec_steps"):
+        runner.spec_steps = 0                             # no speculative decode-graph step
+    stats = {"lookup_calls": 0, "lookup_drafted": 0, "lookup_accepted": 0, "lookup_dropped_roundtrip": 0,
+             "lookup_retokenized": 0}
+    # ids every suffix is expected to re-tokenize to in the next call: the ids its last call's scores
+    # were computed on, followed by the tokens it gained
+    expected = [[None for _ in sfx] for _, sfx in original_prompts]
+    decode = (lambda seqs: tok.batch_decode(seqs)) if hasattr(tok, "batch_decode") else (
+        lambda seqs: [tok.decode(t) for t in seqs])
+    while n_p and any(len(g) < G for gp in gen for g in gp):
+        t_step = time.perf_counter()
+        runner.sample_step = stats["lookup_calls"]
+        runner.prompt_base = 0
+        base = runner.tokenize(input_prompts)            # ids of s + decode(generated)
+        # The scores of an accepted position j were computed on base + draft[:j]; the plain loop
+        # computes them on the ids of s + decode(generated + draft[:j]).  The round trip below
+        # checks the whole draft only: where decoding and re-tokenizing is not prefix-stable (a
+        # merging tokenizer) the two can differ, which shows here, one call later, and is counted
+        for pi, tp in enumerate(base):
+            for si, ids in enumerate(tp.suffixes):
+                if expected[pi][si] is not None and list(ids) != expected[pi][si]:
+                    stats["lookup_retokenized"] += 1
+        drafts = []
+        for pi, tp in enumerate(base):
+            row = []
+            for si, ids in enumerate(tp.suffixes):
+                room = min(D, G - len(gen[pi][si]) - 1)
+                d = drafter(np.asarray(list(tp.prefix) + list(ids), dtype=np.int64), N, room) if room > 0 else ()
+                row.append([int(t) for t in d][:max(room, 0)])
+            drafts.append(row)
+        tps = base
+        if any(d for row in drafts for d in row):
+            flat = [gen[pi][si] + d for pi, row in enumerate(drafts) for si, d in enumerate(row)]
+            texts = iter(decode(flat))
+            drafted = [(p, tuple(s + next(texts) for s in sfx)) for p, sfx in original_prompts]
+            with_d = runner.tokenize(drafted)
+            tps = []
+            for pi, (tb, td) in enumerate(zip(base, with_d)):
+                sfxs = []
+                for si, d in enumerate(drafts[pi]):
+                    if d and list(td.suffixes[si]) != list(tb.suffixes[si]) + d:
+                        stats["lookup_dropped_roundtrip"] += 1
+                        drafts[pi][si] = d = []
+                    sfxs.append(list(tb.suffixes[si]) + d)
+                tps.append(TokenizedPrompt(list(tb.prefix), sfxs, max((len(x) for x in sfxs), default=0),
+                                           [len(x) - 1 for x in sfxs]))
+        if any(d for row in drafts for d in row):
+            outs = runner.run_tokenized(tps, drafts=drafts)
+            toks = runner.last_tokens
+            probs = runner.last_token_probs if top_k else None
+        else:
+            # no draft in this call: today's path, one scored row per suffix
+            full = runner.run_tokenized(base)
+            dev_tok = getattr(runner, "last_tokens", None)
+            if not dev_tok or len(dev_tok) != len(full) or any(t is None for t in dev_tok):
+                dev_tok = ([o["id"][:, :, 0].astype(np.int64) for o in full] if top_k
+                           else [greedy_tokens(o) for o in full])
+            outs = [[o[si] for si in range(o.shape[0])] for o in full]
+            toks = [[t[si] for si in range(t.shape[0])] for t in dev_tok]
+            probs = None
+            if top_k:
+                pt = runner.last_token_probs
+                if not pt or any(x is None for x in pt):
+                    pt = [o["p"][:, :, 0] for o in full]
+                probs = [[x[si] for si in range(x.shape[0])] for x in pt]
+        stats["lookup_calls"] += 1
+        for pi in range(n_p):
+            for si, d in enumerate(drafts[pi]):
+                g = gen[pi][si]
+                if len(g) >= G:
+                    continue                              # finished: rode along, scores discarded
+                t = [int(x) for x in np.asarray(toks[pi][si]).reshape(-1)]
+                take = min(len(t), G - len(g))
+                stats["lookup_drafted"] += len(d)
+                stats["lookup_accepted"] += len(t) - 1
+                g.extend(t[:take])
+                expected[pi][si] = list(base[pi].suffixes[si]) + t[:take]
+                kept_scores[pi][si].append(np.asarray(outs[pi][si])[:take])
+                if top_k:
+                    kept_probs[pi][si].append(np.asarray(probs[pi][si]).reshape(-1)[:take])
+        flat = [g for gp in gen for g in gp]
+        texts = iter(decode(flat))
+        input_prompts = [(p, tuple(s + next(texts) for s in sfx)) for p, sfx in original_prompts]
+        if step_times is not None:
+            step_times.append(time.perf_counter() - t_step)
+        if getattr(args, "verbose", False):
+            print(f"call {stats['lookup_calls'] - 1}: {time.perf_counter() - t_step:.3f}s, "
+                  f"{stats['lookup_accepted']} of {stats['lookup_drafted']} draft tokens accepted so far", flush=True)
+    if lookup_stats is not None:
+        lookup_stats.update(stats)
+    # [n_s, num_gen_token, V] (score_top_k: K) per prompt, as the one-token-per-call loop returns
+    output_scores = [np.stack([np.concatenate(rows, axis=0) for rows in ks], axis=0) if ks else np.zeros((0, G, 0))
+                     for ks in kept_scores]
+    if top_k and token_record is not None:
+        token_record["token_ids"] = [np.asarray(gp, dtype=np.int64).reshape(len(gp), G) for gp in gen]
+        token_record["token_probs"] = [np.stack([np.concatenate(x) for x in kp], axis=0).astype(np.float16)
+                                       if kp else np.zeros((0, G), np.float16) for kp in kept_probs]
+    return output_scores, input_prompts
+
+
 def greedy_tokens(scores: np.ndarray) -> np.ndarray:
     """np.argmax(scores, axis=-1) (first index on ties).  fp16 probabilities are >= 0, whose bit
     patterns order like their values: the argmax runs on the uint16 view (numpy has no fast fp16
@@ -438,6 +579,7 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     t_build = time.perf_counter() - t0
     t1 = time.perf_counter()
     step_times: List[float] = []
+    lk: dict = {}                      # --lookup_decoding: call and acceptance counts
     if getattr(args, "score_mode", "next_token") == "loglik":
         # one scoring pass, no greedy token to append: the prompts are written back as they came;
         # the output file holds the [n_s, 3] arrays and the per-token log-probabilities
@@ -447,7 +589,8 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
         step_times.append(time.perf_counter() - t1)
     else:
         rec: dict = {}
-        scores, updated = generation_loop(args, runner, comm, tok, original, step_times, token_record=rec)
+        scores, updated = generation_loop(args, runner, comm, tok, original, step_times, token_record=rec,
+                                          lookup_stats=lk)
         if getattr(runner, "score_top_k", 0):
             # compact scores: the K best (id, probability) pairs of every suffix and step, and the
             # appended tokens with their probabilities
@@ -465,6 +608,10 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     sampling = SamplingParams.from_args(args)
     metrics["sampling"] = sampling.as_dict() if sampling is not None else {"do_sample": False}
     metrics["score_top_k"] = int(getattr(runner, "score_top_k", 0))
+    if getattr(args, "lookup_decoding", 0):
+        metrics["lookup_decoding"] = int(args.lookup_decoding)
+        metrics["lookup_ngram"] = int(getattr(args, "lookup_ngram", 3))
+        metrics.update({k: int(v) for k, v in lk.items()})
     metrics["score_d2h_bytes_last_pass"] = int(getattr(runner, "score_d2h_bytes", 0))
     if device.type == "cuda":
         metrics["peak_hbm_bytes"] = torch.cuda.max_memory_allocated(device)

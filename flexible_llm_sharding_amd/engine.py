@@ -118,6 +118,10 @@ class ShardedRunner:
         # last call's probability of each suffix's chosen token (score_top_k): fp16 [n_s, 1] per prompt
         self.last_token_probs: List[Optional[np.ndarray]] = []
         self.score_d2h_bytes = 0           # bytes of scores the last call copied to the host
+        # prompt-lookup drafts (run_tokenized(drafts=...)): the last such call's accepted draft tokens
+        # per prompt ([n_s] int64), and the rows it scored / kept
+        self.last_accept: List[Optional[np.ndarray]] = []
+        self.lookup_rows = self.lookup_kept = 0
         self.sample_step = 0               # the generation step of the next call (api.generation_loop)
         self.prompt_base = 0               # index in the prompt file of the next call's first prompt
         self._sample_table: Optional[torch.Tensor] = None
@@ -500,14 +504,53 @@ class ShardedRunner:
                 if min(ids) < 0 or max(ids) >= V:
                     raise ValueError(f"score_mode='loglik': suffix {s} of prompt {i} holds a token id outside [0, {V})")
 
-    def run_tokenized(self, tps: Sequence[TokenizedPrompt]) -> List[Optional[np.ndarray]]:
+    def _check_drafts(self, tps, drafts) -> List[List[int]]:
+        """A call with prompt-lookup drafts, validated before any launch -> the rows scored per
+        suffix (its last token before the draft, then one per draft token)."""
+        V = self.cfg.vocab_size
+        if not self.row_exact:
+            raise ValueError("drafts need the prefix K/V cache and exact_reuse (row-exact calls): a verified "
+                             "row's scores must be those of the call that computes it alone")
+        for on, what in ((self.loglik, "score_mode='loglik'"), (self.sampling is not None, "sampling"),
+                         (self.hip_graphs, "hip_graphs"), (self.plan.mode != "single", "several ranks"),
+                         (bool(self.resume_dir), "resume_dir")):
+            if on:
+                raise ValueError(f"drafts do not combine with {what}")
+        if len(drafts) != len(tps):
+            raise ValueError("drafts: one list per prompt expected")
+        counts = []
+        for i, (tp, ds) in enumerate(zip(tps, drafts)):
+            if len(ds) != len(tp.suffixes):
+                raise ValueError(f"drafts: prompt {i} has {len(tp.suffixes)} suffixes and {len(ds)} drafts")
+            row = []
+            for si, (ids, d) in enumerate(zip(tp.suffixes, ds)):
+                d = [int(t) for t in d]
+                if len(d) >= len(ids) or (d and list(ids[len(ids) - len(d):]) != d):
+                    raise ValueError(f"drafts: suffix {si} of prompt {i} does not end with its draft")
+                if d and (min(d) < 0 or max(d) >= V):
+                    raise ValueError(f"drafts: suffix {si} of prompt {i} holds a token id outside [0, {V})")
+                row.append(len(d) + 1)
+            counts.append(row)
+        return counts
+
+    def run_tokenized(self, tps: Sequence[TokenizedPrompt], drafts=None) -> List[Optional[np.ndarray]]:
+        """One call on tokenized prompts.  ``drafts`` (prompt-lookup decoding, lookup.py): per
+        prompt and suffix the draft tokens its ids END with.  The call then scores every suffix's
+        last token before the draft and each draft token, verifies them on the device
+        (``ops.verify_rows``) and returns per prompt a LIST with one array per suffix: the scores of
+        its kept rows — the accepted draft positions and the one after them — [kept, V] fp16 (or
+        ``TOPK_DTYPE`` [kept, K]); ``last_tokens`` / ``last_token_probs`` hold per prompt a list of
+        [kept] arrays (each kept row's greedy token), ``last_accept`` the accepted counts.  Rejected
+        rows never leave the device.  Such a call runs eagerly (no decode graph) and row-exact."""
         t_start = time.perf_counter()
         spec, self._spec = self._spec, None
         if spec is not None:
-            if self._spec_matches(spec, tps):
+            if drafts is None and self._spec_matches(spec, tps):
                 return self._finish_spec(spec, tps, t_start)
             self._drop_spec(spec)
         n = len(tps)
+        score_rows = self._check_drafts(tps, drafts) if drafts is not None else None
+        self.lookup_rows = self.lookup_kept = 0
         if self.loglik:
             self._check_loglik(tps)
             self._pair_lens = [[len(s) for s in tp.suffixes] for tp in tps]
@@ -515,7 +558,7 @@ class ShardedRunner:
         window = self._call_window(tps)
         entry, cached = self._prefix_entry(tps)
         if self._vram_cap:
-            self._plan_call(tps, cached)
+            self._plan_call(tps, cached, scored_rows=sum(map(sum, score_rows)) if score_rows is not None else 0)
         groups = split_microbatches(tps, self.micro_budget(tps, cached), suffix_only=cached)
         # suffix K/V reuse (runtime/prefix_cache.py): rows of every suffix in the entry, and with a
         # cached entry the leading tokens each suffix shares with the last call's (not recomputed)
@@ -523,14 +566,26 @@ class ShardedRunner:
                               if entry is not None else (None, None))
         if sfx_keep is not None and not any(k for ks in sfx_keep for k in ks):
             sfx_keep = None          # nothing to reuse: keep the multi-suffix work items
+        if sfx_keep is not None and score_rows is not None:
+            # every scored row is computed in this call (the rows of a rejected draft are overwritten)
+            sfx_keep = [[min(k, len(s) - c) for k, s, c in zip(ks, tp.suffixes, cs)]
+                        for ks, tp, cs in zip(sfx_keep, tps, score_rows)]
         kept = sum(k for ks in sfx_keep for k in ks) if sfx_keep is not None else 0
         batches = [pack_prompts([tps[i] for i in g], g, self.prefix_attention,
                                 prefix_offsets=[entry.offsets[i] for i in g] if entry is not None else None,
                                 kv_cached=cached, q_block=self.q_block,
                                 suffix_rows=[sfx_rows[i] for i in g] if sfx_rows is not None else None,
                                 suffix_keep=[sfx_keep[i] for i in g] if sfx_keep is not None else None,
-                                single_suffix_items=self.row_exact, window=window, loglik=self.loglik)
+                                single_suffix_items=self.row_exact, window=window, loglik=self.loglik,
+                                score_rows=[score_rows[i] for i in g] if score_rows is not None else None)
                    for g in groups]
+        if score_rows is not None:
+            for b, g in zip(batches, groups):
+                cnt = np.asarray([c for i in g for c in score_rows[i]], dtype=np.int64)
+                b.row_start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+                # row j of a suffix predicts draft token j; its last row predicts the new token
+                b.draft = np.concatenate([np.asarray(list(d) + [-1], dtype=np.int32)
+                                          for i in g for d in drafts[i]]).astype(np.int32)
         t_pack = time.perf_counter() - t_start
         if self.hip_graphs:
             with self._workspace():
@@ -538,7 +593,8 @@ class ShardedRunner:
         self.ctx.prefix_entry = entry
         try:
             with self._workspace(), self._row_exact(self.row_exact):
-                if self._decode_graphable(batches, cached) and not entry.host:    # (graphs: K/V in HBM)
+                if (self._decode_graphable(batches, cached) and not entry.host      # (graphs: K/V in HBM)
+                        and drafts is None):
                     outputs = self._run_graphed(tps, batches, t_start, entry=entry)
                 else:
                     outputs = self._run_batches(tps, batches, t_start)
@@ -562,7 +618,7 @@ class ShardedRunner:
         self.stats["host_pack_s"] = t_pack
         return outputs
 
-    def _plan_call(self, tps, cached: bool) -> None:
+    def _plan_call(self, tps, cached: bool, scored_rows: int = 0) -> None:
         """--max_vram_gb: re-plan micro-batch and chunk sizes for this call's token count (one
         micro-batch whenever the cap allows it: the hidden state then never leaves HBM)."""
         from .runtime.memplan import plan_for_vram
@@ -579,7 +635,8 @@ class ShardedRunner:
                                         weight_bytes=self.prefetcher.planned_hbm_bytes() if self.cuda else None,
                                         fused_norm=self.ctx.fused_norm, extra_bytes=stage,
                                         grouped=self.prefix_cache is None,
-                                        scored_rows=sum(len(s) for tp in tps for s in tp.suffixes) if self.loglik else 0)
+                                        scored_rows=(sum(len(s) for tp in tps for s in tp.suffixes) if self.loglik
+                                                     else scored_rows))
         if self.loglik and self.ctx.ws is not None and (mc, ar, qc) != (self.ctx.mlp_chunk, self.ctx.attn_rows,
                                                                           self.ctx.qkv_chunk):
             # the norm state grows with the call's scored pairs and the plan shrinks the chunks to
@@ -953,6 +1010,7 @@ class ShardedRunner:
             rx_stats = {f"rx_{k}": float(v) for k, v in px.inbox.stats.items()}
         self.last_tokens = [None] * len(px.tps)
         self.last_token_probs = [None] * len(px.tps)
+        self.last_accept = [None] * len(px.tps)
         self.score_d2h_bytes = 0
         for batch, host, ev, pool_buf, am in px.out_pending:
             self._collect(batch, host.numpy(), am, px.outputs)
@@ -1381,6 +1439,8 @@ class ShardedRunner:
     def _collect(self, batch: PackedBatch, probs: np.ndarray, am, outputs) -> None:
         """Host scores of a finished micro-batch into ``outputs`` (prompt order) and its greedy
         tokens into ``self.last_tokens`` (``am``: the rows' argmax, computed on the device)."""
+        if isinstance(am, dict):
+            return self._collect_lookup(batch, probs, am, outputs)
         self.score_d2h_bytes += probs.nbytes + (4 * am.numel() if am is not None else 0)
         if self.loglik:
             return self._collect_loglik(batch, probs, outputs)
@@ -1475,10 +1535,122 @@ class ShardedRunner:
             self.last_token_probs[pid] = pv[r:r + ns].copy().reshape(ns, 1)
             r += ns
 
+    # ------------------------------------------------- prompt-lookup drafts (run_tokenized(drafts=...))
+    def _start_lookup_copy(self, batch: PackedBatch, probs: torch.Tensor):
+        """A drafted micro-batch's output: ``ops.verify_rows`` on its scored rows, then the D2H of
+        the KEPT rows only (gathered by ``copy_rows`` into a compact device buffer, from there
+        into the pooled pinned buffer; ``score_top_k``: ``topk_rows`` on the kept rows).  The host
+        waits once, for the accepted counts (a few ints): they size the copy."""
+        meta = batch.device_tensors(self.dev)
+        tok, accept, keep, n_kept = self.ops.verify_rows(probs, meta["row_start"], meta["draft"])
+        n_sfx = accept.shape[0]
+        if self.cuda:
+            # accept and n_kept are one [n_sfx + 1] vector on the device (ops.verify_rows): one copy
+            # into a pooled pinned buffer, and the host waits for that copy alone
+            dev_ctrl = accept.as_strided((n_sfx + 1,), (1,))
+            assert dev_ctrl[n_sfx:].data_ptr() == n_kept.data_ptr()
+            ctrl_buf = self._get_store().host_buffer(4 * (n_sfx + 1))
+            ctrl = ctrl_buf[:4 * (n_sfx + 1)].view(torch.int32)
+            ctrl.copy_(dev_ctrl, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.dev))
+            done.synchronize()
+        else:
+            ctrl_buf, ctrl = None, torch.cat([accept, n_kept]).cpu()
+        acc = ctrl[:n_sfx].numpy().astype(np.int64)
+        nk = int(ctrl[n_sfx])
+        if ctrl_buf is not None:
+            self._get_store().recycle_host(ctrl_buf)
+        if nk != int(acc.sum()) + n_sfx:
+            raise RuntimeError(f"verify_rows kept {nk} rows for accepted counts summing to {int(acc.sum())} "
+                               f"over {n_sfx} suffixes")
+        idx = keep[:nk]
+        kept = self._gather_kept(probs, idx)                     # [kept, V]: what crosses PCIe
+        tok_k = tok.index_select(0, idx.long()).contiguous()
+        extra = {"accept": acc, "rows": int(probs.shape[0]), "kept": nk}
+        if self.score_top_k:
+            host, pool_buf = self._topk_to_host(kept, tok_k, self.d2h_stream)
+            ev = None
+            if self.cuda:
+                ev = torch.cuda.Event()
+                ev.record(self.d2h_stream)
+            return batch, host, ev, pool_buf, extra
+        if not self.cuda:
+            extra["tok"] = tok_k.cpu().numpy()
+            return batch, kept.detach().to(torch.float16).cpu(), None, None, extra
+        store = self._get_store()
+        nbytes = kept.numel() * kept.element_size()
+        pool_buf = store.host_buffer(nbytes + 4 * nk)
+        host = pool_buf[:nbytes].view(kept.dtype).view(kept.shape)
+        host_tok = pool_buf[nbytes:nbytes + 4 * nk].view(torch.int32)
+        self.d2h_stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.d2h_stream):
+            host.copy_(kept, non_blocking=True)
+            kept.record_stream(self.d2h_stream)
+            host_tok.copy_(tok_k, non_blocking=True)
+            tok_k.record_stream(self.d2h_stream)
+            ev = torch.cuda.Event()
+            ev.record(self.d2h_stream)
+        extra["tok"] = host_tok
+        return batch, host, ev, pool_buf, extra
+
+    def _gather_kept(self, probs: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        """probs[idx] as a compact [len(idx), V] tensor: ``copy_rows`` (16 bytes per lane) where the
+        rows allow it, ``index_select`` for a vocabulary that is no multiple of 8 (Granite's 49,155)."""
+        if probs.shape[1] % 8 == 0 and probs.stride(0) % 8 == 0 and probs.data_ptr() % 16 == 0:
+            return self.ops.gather_rows(probs, idx)
+        return probs.index_select(0, idx.long())
+
+    def _collect_lookup(self, batch: PackedBatch, host: np.ndarray, extra: dict, outputs) -> None:
+        """A drafted micro-batch's kept rows split back into prompts and suffixes: per prompt a
+        list of [kept, V] fp16 (``score_top_k``: ``TOPK_DTYPE`` [kept, K]) arrays into ``outputs``,
+        of [kept] int64 tokens into ``last_tokens`` (and fp16 probabilities into
+        ``last_token_probs``), and the accepted counts into ``last_accept``."""
+        acc, nk, K = extra["accept"], extra["kept"], self.score_top_k
+        self.lookup_rows += extra["rows"]
+        self.lookup_kept += nk
+        self.score_d2h_bytes += host.nbytes + (0 if K else 4 * nk)
+        pv = None
+        if K:
+            o_tok, o_vals, o_pv, total = self._topk_offsets(nk)
+            assert host.dtype == np.uint8 and host.size == total, (host.dtype, host.size, total)
+            ids = host[:o_tok].view(np.int32).reshape(nk, K)
+            tok = host[o_tok:o_vals].view(np.int32)
+            vals = host[o_vals:o_pv].view(np.float16).reshape(nk, K)
+            pv = host[o_pv:total].view(np.float16)
+        else:
+            tok = extra["tok"]
+            tok = tok.numpy() if isinstance(tok, torch.Tensor) else tok
+            assert host.shape[0] == nk, (host.shape, nk)
+        r = i = 0
+        for j, pid in enumerate(batch.prompt_ids):
+            ns = batch.n_suffix[j]
+            outs, toks, pvs = [], [], []
+            for a in acc[i:i + ns]:
+                n = int(a) + 1
+                if K:
+                    out = np.empty((n, K), dtype=TOPK_DTYPE)
+                    out["id"], out["p"] = ids[r:r + n], vals[r:r + n]
+                    pvs.append(pv[r:r + n].copy())
+                else:
+                    out = host[r:r + n].astype(np.float16, copy=True)
+                outs.append(out)
+                toks.append(tok[r:r + n].astype(np.int64))
+                r += n
+            outputs[pid] = outs
+            self.last_tokens[pid] = toks
+            self.last_token_probs[pid] = pvs if K else None
+            self.last_accept[pid] = acc[i:i + ns].copy()
+            i += ns
+        assert r == nk and i == acc.shape[0], (r, nk, i, acc.shape)
+
     def _start_output_copy(self, batch: PackedBatch, probs: torch.Tensor):
         """D2H of a micro-batch's probabilities and of their row argmax (the greedy token of
         each suffix: api.generation_loop needs no host pass over the [n_s, V] scores).
-        ``score_top_k``: of the K best entries and the tokens' probabilities instead."""
+        ``score_top_k``: of the K best entries and the tokens' probabilities instead.
+        A drafted micro-batch (prompt-lookup decoding): of its kept rows (``_start_lookup_copy``)."""
+        if batch.draft is not None:
+            return self._start_lookup_copy(batch, probs)
         if self.score_top_k:
             am = self._pick_rows(batch, probs, self.sample_step)
             host, pool_buf = self._topk_to_host(probs, am, self.d2h_stream)

@@ -575,6 +575,37 @@ class HipOps:
                                   pv.data_ptr() if pv is not None else None, _stream()), "fls_topk_rows")
         return ids, vals, pv
 
+    def verify_rows(self, probs, row_start, draft):
+        """(tok int32 [R], accept int32 [n_sfx], keep int32 [R], n_kept int32 [1]): prompt-lookup
+        draft verification of fp16 probabilities (lookup.py holds the definition).  ``row_start``:
+        int32 CUDA [n_sfx + 1], the first row of every suffix; ``draft``: int32 CUDA [R], the draft
+        token scored next to each row (-1 on a suffix's last row).  ``keep[:n_kept]`` are the kept
+        rows in suffix order; ``accept`` and ``n_kept`` are views of one [n_sfx + 1] vector (one D2H
+        copy fetches both); nothing here waits for the device."""
+        _f16(probs, "probs")
+        if probs.dim() != 2:
+            raise TypeError("probs must be a [rows, V] tensor")
+        rows, V = probs.shape
+        if probs.stride(1) != 1 or probs.stride(0) < V:
+            raise TypeError("probs must have unit column stride and a row stride >= V")
+        for t, name in ((row_start, "row_start"), (draft, "draft")):
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise TypeError(f"{name} must be a contiguous int32 CUDA vector")
+            if t.device != probs.device:
+                raise TypeError(f"probs and {name} must be on one device")
+        if row_start.numel() < 1 or draft.numel() != rows:
+            raise TypeError(f"row_start needs n_sfx + 1 entries and draft {rows}, got {row_start.numel()} and "
+                            f"{draft.numel()}")
+        n = row_start.numel() - 1
+        # one allocation: [accept | n_kept | tok | keep]
+        buf = torch.empty(n + 1 + 2 * rows, dtype=torch.int32, device=probs.device)
+        accept, n_kept = buf[:n], buf[n:n + 1]
+        tok, keep = buf[n + 1:n + 1 + rows], buf[n + 1 + rows:]
+        _chk(self.k.fls_verify_rows(probs.data_ptr(), probs.stride(0), rows, V, row_start.data_ptr(), n,
+                                    draft.data_ptr(), tok.data_ptr(), accept.data_ptr(), keep.data_ptr(),
+                                    n_kept.data_ptr(), _stream()), "fls_verify_rows")
+        return tok, accept, keep, n_kept
+
     def lm_head_softmax(self, h, w, logits_scaling: float = 1.0):
         return self.softmax(self.linear(h, w), logits_scaling)
 

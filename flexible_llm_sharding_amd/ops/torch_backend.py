@@ -268,6 +268,34 @@ class TorchOps:
             pv = torch.from_numpy(picked_keys(p16, picked.cpu().numpy()).view(np.float16)).to(probs.device)
         return (torch.from_numpy(ids).to(probs.device), torch.from_numpy(vals.view(np.float16)).to(probs.device), pv)
 
+    def verify_rows(self, probs: torch.Tensor, row_start: torch.Tensor, draft: torch.Tensor):
+        """HipOps.verify_rows on the host -> (tok [R], accept [n_sfx], keep [R], n_kept [1]), int32:
+        the greedy id of every row (``argmax_rows``), per suffix the number of leading rows whose id
+        equals their draft token, and the kept rows (rows 0 .. accept of every suffix, in suffix
+        order) in ``keep[:n_kept]`` (lookup.verify_rows: the same entries)."""
+        if probs.dim() != 2:
+            raise TypeError("probs must be a [rows, V] tensor")
+        rows = probs.shape[0]
+        if row_start.dtype != torch.int32 or draft.dtype != torch.int32 or draft.numel() != rows:
+            raise TypeError(f"row_start and draft must be int32 vectors (draft: {rows} entries)")
+        dev = probs.device
+        tok = self.argmax_rows(probs)                 # (the rule of this backend's greedy token)
+        t, rs, dr = tok.cpu().numpy(), row_start.cpu().numpy(), draft.cpu().numpy()
+        n = rs.shape[0] - 1
+        accept = np.zeros(n, dtype=np.int32)
+        keep = np.zeros(rows, dtype=np.int32)
+        k = 0
+        for i in range(n):
+            a, r0, r1 = 0, int(rs[i]), int(rs[i + 1])
+            while r0 + a < r1 - 1 and t[r0 + a] == dr[r0 + a]:
+                a += 1
+            accept[i] = a
+            if r1 > r0:
+                keep[k:k + a + 1] = np.arange(r0, r0 + a + 1)
+                k += a + 1
+        ctrl = torch.from_numpy(np.concatenate([accept, [k]]).astype(np.int32)).to(dev)   # [accept | n_kept], as HipOps
+        return tok, ctrl[:n], torch.from_numpy(keep).to(dev), ctrl[n:]
+
     def softmax(self, logits: torch.Tensor, logits_scaling: float = 1.0) -> torch.Tensor:
         if logits_scaling != 1.0:                            # Granite: logits / logits_scaling
             logits = logits / logits_scaling

@@ -102,6 +102,11 @@ class PackedBatch:
                                                 # ``prompt_scored`` then range over (row, target) pairs
                                                 # (``last_segments`` / ``work_last`` stay per suffix: such a
                                                 # batch runs the unpruned last layer, which reads neither)
+    row_start: Optional[np.ndarray] = None      # prompt-lookup drafts (``pack_prompts(score_rows=...)`` scores
+                                                # several trailing rows per suffix): [n_sfx + 1] int32, each
+                                                # suffix's range of ``last_idx`` ...
+    draft: Optional[np.ndarray] = None          # ... and [S_total] int32 the draft token scored next to each
+                                                # scored row, -1 on a suffix's last (ops.verify_rows)
     _dev: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -202,7 +207,7 @@ class PackedBatch:
              "last_idx": self.last_idx, "last_pos": self.positions[self.last_idx].astype(np.int32),
              "work_last": self.work_last}
         for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win",
-                     "r0_lo", "r0_item", "r0_item_last", "targets"):
+                     "r0_lo", "r0_item", "r0_item_last", "targets", "row_start", "draft"):
             v = getattr(self, name)
             if v is not None:
                 m[name] = v
@@ -224,7 +229,8 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                  kv_cached: bool = False, q_block: int = Q_BLOCK,
                  suffix_rows: Optional[Sequence[Sequence[int]]] = None,
                  suffix_keep: Optional[Sequence[Sequence[int]]] = None,
-                 single_suffix_items: bool = False, window: int = 0, loglik: bool = False) -> PackedBatch:
+                 single_suffix_items: bool = False, window: int = 0, loglik: bool = False,
+                 score_rows: Optional[Sequence[Sequence[int]]] = None) -> PackedBatch:
     """Pack prompts into one token matrix + attention work items.
 
     ``prefix_offsets`` (rows of each prompt's prefix in a PrefixEntry) turns on
@@ -256,7 +262,16 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     scored at the prompt's last prefix row (repeated once per suffix), token t >= 1 at the suffix's
     row t - 1; the last row of a suffix scores nothing.  Every suffix needs a token and every
     prompt a prefix row; not with ``kv_cached`` or ``suffix_keep`` (the prefix rows are not packed).
+
+    ``score_rows[j][s]`` (prompt-lookup drafts): the number k >= 1 of trailing rows of suffix s of
+    prompt j that are scored — its last token before the draft and every draft token — instead of
+    the last one alone; each needs a packed row (k <= the suffix's tokens less its kept ones).
+    ``last_idx``, ``last_segments``, ``work_last`` (one single-query item per scored row, as for
+    the last row today) and the pruned last layer's scored set then hold k entries per suffix, in
+    row order.  None, or 1 everywhere, is the packing without it, byte for byte.
     """
+    if score_rows is not None and loglik:
+        raise ValueError("score_rows does not combine with loglik packing")
     if loglik and (kv_cached or suffix_keep is not None):
         raise ValueError("loglik packing does not combine with kv_cached / suffix_keep")
     if window < 0:
@@ -313,6 +328,9 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             c = keep[si] if keep is not None else 0
             c0_row = suffix_rows[j][si] if suffix_rows is not None else -1
             n = len(s) - c
+            k_sc = int(score_rows[j][si]) if score_rows is not None else 1
+            if not 1 <= k_sc <= max(n, 1):
+                raise ValueError(f"score_rows: suffix {si} of prompt {prompt_ids[j]} scores {k_sc} of {n} packed rows")
             s0 = t
             ids.append(np.asarray(s[c:], dtype=np.int32))
             pos.append(np.arange(Lp + c, Lp + c + n, dtype=np.int32))
@@ -323,10 +341,10 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             sfx_of.extend([si] * n)
             if W:
                 r0_lo.append(np.clip(np.arange(Lp + c, Lp + c + n, dtype=np.int32) - (W - 1), 0, Lp))
-                r0_item_last.append((int(r0_lo[-1][-1]),) * 2)
+                r0_item_last.extend((int(v),) * 2 for v in r0_lo[-1][n - k_sc:])
             r2s, r2l = (c0_row, c) if c else (0, 0)
             segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l, window=W))
-            last.append(s0 + n - 1)
+            last.extend(range(s0 + n - k_sc, s0 + n))
             if loglik:
                 if n == 0:
                     raise ValueError(f"loglik: suffix {si} of prompt {prompt_ids[j]} has no token")
@@ -335,15 +353,17 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                 pair_rows.append(rows)
                 pair_tgt.append(np.asarray(s, dtype=np.int32))
                 n_pairs += n
-            # the scored row alone, for a last decoder layer that computes only scored rows
-            lsegs.append(Segment(s0 + n - 1, 1, p0, Lp, 0, s0, n, q_off=n - 1, r2_start=r2s, r2_len=r2l,
-                                 window=W))
-            if keep is not None:
-                # its work item (HIP): the whole suffix from the cache through the row's window
-                lwork.append((s0 + n - 1, 1, 0, p0, Lp, 0, 0, 0))
-                # (windowed: from the 64-row tile of the scored row's first visible cache row)
-                wl = max(c + n - W, 0) // 64 * 64 if W else 0
-                lwork2.append((c0_row + wl, c + n - wl))
+            # the scored row alone, for a last decoder layer that computes only scored rows (row i of
+            # the packed suffix sees the suffix up to itself: one row today, the last)
+            for i in range(n - k_sc, n):
+                lsegs.append(Segment(s0 + i, 1, p0, Lp, 0, s0, i + 1, q_off=i, r2_start=r2s, r2_len=r2l,
+                                     window=W))
+                if keep is not None:
+                    # its work item (HIP): the whole suffix from the cache through the row's window
+                    lwork.append((s0 + i, 1, 0, p0, Lp, 0, 0, 0))
+                    # (windowed: from the 64-row tile of the scored row's first visible cache row)
+                    wl = max(c + i + 1 - W, 0) // 64 * 64 if W else 0
+                    lwork2.append((c0_row + wl, c + i + 1 - wl))
             if c0_row >= 0:
                 sfx_src.append(np.arange(s0, s0 + n, dtype=np.int32))
                 sfx_dst.append(np.arange(c0_row + c, c0_row + c + n, dtype=np.int32))

@@ -83,6 +83,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "0 (default): off; at most 1024 and the vocabulary size.  Tokens, probabilities and "
                         "updated prompts are those of the run without the flag.  Not with --score_mode loglik, nor "
                         "with --do_sample on several GPUs or with --num_batch > 1")
+    p.add_argument("--lookup_decoding", type=int, default=0, metavar="D",
+                   help="prompt-lookup speculative generation: every call also scores up to D draft tokens per "
+                        "suffix, guessed from the latest earlier occurrence of the text's last n-gram "
+                        "(--lookup_ngram), and keeps those the greedy decoding produces itself, so a call can "
+                        "yield up to D + 1 tokens per suffix.  Output files are those of the run without the flag "
+                        "(every call is row-exact); only the number of calls changes.  0 (default): off; 1..16.  "
+                        "Greedy, one GPU, --num_batch 1; not with --do_sample, --score_mode loglik, --hip_graphs, "
+                        "--prefix_kv_cache / --suffix_kv_cache / --exact_reuse false or --resume_dir")
+    p.add_argument("--lookup_ngram", type=int, default=3, metavar="N",
+                   help="with --lookup_decoding: the longest n-gram tried (n = N .. 1, the first that occurs "
+                        "earlier in the text decides); 1..8")
     p.add_argument("--hip_graphs", type=str2bool, nargs="?", const=True, default=False,
                    help="with --resident: capture each micro-batch's whole forward as one HIP graph and "
                         "replay it (shape-bucketed; removes per-op host dispatch for small batches)")
@@ -201,9 +212,32 @@ def check_top_k(args, world: int = 1) -> None:
                          "the host sampler needs the full rows")
 
 
+def check_lookup(args, world: int = 1) -> None:
+    """``--lookup_decoding`` / ``--lookup_ngram``: values in range, and with D > 0 none of the modes
+    the verification is not built for — it is greedy, row-exact, on one rank and one batch; a
+    ``ValueError`` names the flag."""
+    from ..lookup import DEFAULT_NGRAM, check_lookup_values
+    d, _ = check_lookup_values(getattr(args, "lookup_decoding", 0), getattr(args, "lookup_ngram", DEFAULT_NGRAM))
+    if d == 0:
+        return
+    ngpu = getattr(args, "num_gpus", None)
+    for bad, flag in ((getattr(args, "do_sample", False), "--do_sample (verification is greedy)"),
+                      (getattr(args, "score_mode", "next_token") == "loglik", "--score_mode loglik"),
+                      (getattr(args, "hip_graphs", False), "--hip_graphs"),
+                      (getattr(args, "prefix_kv_cache", "auto") is False, "--prefix_kv_cache false"),
+                      (getattr(args, "suffix_kv_cache", "auto") is False, "--suffix_kv_cache false"),
+                      (getattr(args, "exact_reuse", True) is False, "--exact_reuse false"),
+                      (getattr(args, "resume_dir", None), "--resume_dir"),
+                      (world > 1 or (ngpu is not None and ngpu > 1), "more than one GPU (rank)"),
+                      (getattr(args, "num_batch", 1) > 1, "--num_batch > 1")):
+        if bad:
+            raise ValueError(f"--lookup_decoding does not combine with {flag}")
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     check_score_mode(args)
     check_sampling(args)
     check_top_k(args)
+    check_lookup(args)
     return args
