@@ -184,6 +184,17 @@ int fls_topk_rows(const void* probs, int ld, int rows, int V, int K, int* ids, v
 // hipErrorInvalidValue for rows < 0, n_sfx < 0, V <= 0, ld < V or a missing array.
 int fls_verify_rows(const void* probs, int ld, int rows, int V, const int* row_start, int n_sfx, const int* draft,
                     int* tok, int* accept, int* keep, int* n_kept, fls_stream_t s);
+// segment pooling of fp16 rows (csrc/kernels/pooling.hip; flexible_llm_sharding_amd/embed.py holds the
+// definition).  x: n_src rows of H columns, row stride ld >= H.  The row list is row_idx[0 .. n_list)
+// (int32 rows of x; an index outside [0, n_src) is clamped into it) or, with row_idx null, rows
+// 0 .. n_list - 1 of x (n_list <= n_src).  Segment i owns entries seg_start[i] .. seg_start[i + 1] - 1
+// of the list (n_seg + 1 int32, clamped to [0, n_list]).  out[i, 0 .. D) fp32 = the mean over the
+// segment's rows of their first D columns, summed in fp32 in row order (one row: the row itself);
+// normalize != 0: divided by max(||out[i]||_2, 1e-12).  An empty segment gives zeros and reads no row.
+// A segment's result depends on its own rows only.  One launch, two with normalize, on s.
+// hipErrorInvalidValue for a missing array, H <= 0, ld < H, D outside 1 .. H or a list longer than x.
+int fls_pool_rows(const void* x, int ld, int n_src, int H, const int* row_idx, int n_list, const int* seg_start,
+                  int n_seg, int D, int normalize, float* out, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0

@@ -28,13 +28,15 @@ import torch
 
 from . import knobs
 from .config import MAX_TOKEN_LEN, ModelConfig
+from .embed import EmbedParams
+from .embed import layer_names as mode_layer_names
 from .engine import ShardedRunner
 from .parallel.comm import Comm
 from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
 from .sampling import SamplingParams, draws as sample_draws, sample_tokens
-from .utils.cli import check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
+from .utils.cli import check_embed, check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -80,7 +82,8 @@ def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str
 
 
 def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device):
-    names = cfg.layer_names()
+    # (embed mode ends at model.norm: the LM head is neither planned nor read, and need not exist)
+    names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
     plan = make_plan(len(names), args.layer_num_per_shard, comm.world, comm.rank, args.data_parallel,
                      getattr(args, "pipeline_stages", "round_robin"))
     mine = [names[i] for i in sorted({i for sh in plan.my_shards for i in sh})]
@@ -186,8 +189,14 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     check_sampling(args)
     check_top_k(args, comm.world)
     check_lookup(args, comm.world)
-    if getattr(args, "score_mode", "next_token") == "loglik" and comm.world > 1 and not args.data_parallel:
-        raise ValueError("--score_mode loglik does not combine with model parallel: pass --data_parallel")
+    check_embed(args, cfg.hidden_size)
+    mode = getattr(args, "score_mode", "next_token")
+    if mode in ("loglik", "embed") and comm.world > 1 and not args.data_parallel:
+        raise ValueError(f"--score_mode {mode} does not combine with model parallel: pass --data_parallel")
+    embed_kw = {}
+    if mode == "embed":
+        ep = EmbedParams.from_args(args)
+        embed_kw = dict(embed_pooling=ep.pooling, embed_dim=ep.dim, embed_normalize=ep.normalize)
     pkv = resolve_prefix_kv_cache(args)
     skv = resolve_suffix_kv_cache(args, comm.world) and pkv
     n_dec = sum(1 for n in cfg.layer_names() if layer_kind(n) == "decoder")
@@ -218,7 +227,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
             if model <= auto_hbm_cache_bytes(args, cfg, device, reserve, n_slots=0):
                 args = copy.copy(args)
                 args.resident = True
-        wc = resolve_weight_cache(args, cfg, comm, cfg.layer_names(), sliced=True)
+        wc = resolve_weight_cache(args, cfg, comm, mode_layer_names(cfg, mode), sliced=True)
         return build_dp_sharded_runner(args, cfg, device, comm, tok, weight_cache=wc, prefix_kv_cache=pkv)
     src = build_source(args, cfg, comm, device)
     act = None
@@ -246,7 +255,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          # one rank draws the tokens on the device; several ranks: rank 0 draws the
                          # same tokens on the host from the gathered scores (generation_loop)
                          sampling=SamplingParams.from_args(args) if comm.world == 1 else None,
-                         score_top_k=int(getattr(args, "score_top_k", 0) or 0))
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), **embed_kw)
 
 
 def load_model_meta(args):
@@ -292,6 +301,10 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
         return sum((o for o, _ in allv), [])
     if comm.world == 1:
         return outs
+    if getattr(runner, "embed", None) is not None:
+        # float32 [n_s, D] arrays: gathered as objects (gather_scores packs fp16 and would round them)
+        allv = comm.gather_object(outs, dst=0)
+        return sum(allv, []) if comm.rank == 0 else []
     if getattr(runner, "score_top_k", 0):
         # K (id, probability) pairs per row: gathered as objects (gather_scores packs fp16 and
         # cannot carry the ids)
@@ -587,6 +600,14 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
         scores = {"scores": summary, "token_logprobs": list(runner.last_token_logprobs) if comm.rank == 0 else []}
         updated = copy.deepcopy(list(original))
         step_times.append(time.perf_counter() - t1)
+    elif getattr(args, "score_mode", "next_token") == "embed":
+        # one pass, no token to append: the prompts are written back as they came; the output file
+        # holds the [n_s, D] float32 embeddings and how they were pooled
+        ep = runner.embed
+        scores = {"embeddings": run_all(args, runner, comm, list(original)), "pooling": ep.pooling, "dim": ep.dim,
+                  "normalized": ep.normalize}
+        updated = copy.deepcopy(list(original))
+        step_times.append(time.perf_counter() - t1)
     else:
         rec: dict = {}
         scores, updated = generation_loop(args, runner, comm, tok, original, step_times, token_record=rec,
@@ -608,6 +629,10 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     sampling = SamplingParams.from_args(args)
     metrics["sampling"] = sampling.as_dict() if sampling is not None else {"do_sample": False}
     metrics["score_top_k"] = int(getattr(runner, "score_top_k", 0))
+    metrics["score_mode"] = getattr(runner, "score_mode", "next_token")
+    if getattr(runner, "embed", None) is not None:
+        metrics.update({"embed_pooling": runner.embed.pooling, "embed_dim": runner.embed.dim,
+                        "embed_normalize": runner.embed.normalize})
     if getattr(args, "lookup_decoding", 0):
         metrics["lookup_decoding"] = int(args.lookup_decoding)
         metrics["lookup_ngram"] = int(getattr(args, "lookup_ngram", 3))

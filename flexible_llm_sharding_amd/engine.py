@@ -35,6 +35,8 @@ import torch
 
 from . import knobs
 from .config import MAX_TOKEN_LEN, ModelConfig
+from .embed import EmbedParams
+from .embed import layer_names as mode_layer_names
 from .models.layout import layer_kind
 from .models.llama import ExecContext, layer_flops, rope_tables, run_layer
 from .ops import get_ops
@@ -83,13 +85,39 @@ class ShardedRunner:
                  prune_last_layer: bool = True, pipeline_stages: str = "round_robin",
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
                  exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token",
-                 sampling=None, score_top_k: int = 0):
+                 sampling=None, score_top_k: int = 0, embed_pooling: Optional[str] = None,
+                 embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
-        if score_mode not in ("next_token", "loglik"):
-            raise ValueError(f"score_mode={score_mode!r}: 'next_token' or 'loglik'")
+        if score_mode not in ("next_token", "loglik", "embed"):
+            raise ValueError(f"score_mode={score_mode!r}: 'next_token', 'loglik' or 'embed'")
         self.score_mode = score_mode
         self.loglik = score_mode == "loglik"
+        # pooled final hidden states per suffix (embed.py): the pass ends at model.norm, whose rows are
+        # pooled on the device; like loglik it is one full pass, and it draws and ranks no token
+        self.embed: Optional[EmbedParams] = None
+        given = [f for f, v in (("--embed_pooling", embed_pooling), ("--embed_dim", embed_dim),
+                                ("--embed_normalize", embed_normalize)) if v is not None]
+        if score_mode == "embed":
+            world = comm.world if comm is not None else 1
+            for on, flag in ((hip_graphs, "--hip_graphs"), (prefix_kv_cache, "--prefix_kv_cache"),
+                             (suffix_kv_cache, "--suffix_kv_cache"), (resume_dir, "--resume_dir"),
+                             (sampling is not None, "--do_sample"), (score_top_k, "--score_top_k"),
+                             (world > 1 and not data_parallel,
+                              "model parallel (several GPUs without --data_parallel)")):
+                if on:
+                    raise ValueError(f"--score_mode embed does not combine with {flag}")
+            self.embed = EmbedParams(embed_pooling or "last", int(embed_dim or 0),
+                                     True if embed_normalize is None else bool(embed_normalize)
+                                     ).resolved(cfg.hidden_size)
+        elif given:
+            raise ValueError(f"{given[0]} needs --score_mode embed")
+        # every suffix row leaves the last decoder layer (loglik: each is scored; mean pooling: each
+        # is pooled), so that layer runs unpruned and the final norm gathers the rows
+        self._all_suffix_rows = self.loglik or (self.embed is not None and self.embed.pooling == "mean")
+        # (mean pooling's other variant, kept for measurements — set_mean_variant: the last layer
+        # pruned to the suffix rows through pack_prompts(score_rows=...); profiles/embed has both)
+        self._mean_pruned = False
         if self.loglik:
             # continuation log-likelihood: every suffix token is scored in one full pass; the paths
             # that replay, reuse or hand over parts of a pass are not wired for it
@@ -161,7 +189,7 @@ class ShardedRunner:
             # keep that waste near 1% (a VRAM cap re-plans the chunk from the MoE buffer sizes)
             mlp_chunk = MOE_MLP_CHUNK if cfg.is_moe else MLP_CHUNK
         self._plan_req = (token_budget, mlp_chunk, n_slots)
-        self.names = cfg.layer_names()
+        self.names = mode_layer_names(cfg, score_mode)     # (embed: no lm_head)
         self.L = len(self.names)
         self.plan: ShardPlan = make_plan(self.L, layer_num_per_shard, self.comm.world, self.comm.rank,
                                          data_parallel, pipeline_stages)
@@ -234,8 +262,9 @@ class ShardedRunner:
         decs = [n for n in self.names if layer_kind(n) == "decoder"]
         # (loglik scores rows of every suffix position and the last prefix row: the last decoder
         # layer computes every row, and the final norm gathers the scored ones)
-        self.ctx.prune_last = bool(prune_last_layer and decs and not self.loglik)
+        self.ctx.prune_last = bool(prune_last_layer and decs and not self._all_suffix_rows)
         self.ctx.loglik = self.loglik
+        self.ctx.embed = self.embed
         self.ctx.last_decoder = decs[-1] if decs else ""
         my = [s for s in self.plan.my_shards if len(s)]
         self.my_shards = my
@@ -335,6 +364,8 @@ class ShardedRunner:
             return (batch.n_scored, self.cfg.hidden_size)
         if kind in ("embed", "decoder"):
             return (batch.num_tokens, self.cfg.hidden_size)
+        if kind == "norm" and self.embed is not None:
+            return (len(batch.seg_start) - 1, self.embed.dim)      # fp32 pooled embeddings per suffix
         if kind == "norm":
             return (batch.n_scored, self.cfg.hidden_size)
         if self.loglik:
@@ -346,6 +377,8 @@ class ShardedRunner:
         """Reference API: list of (prefix, suffixes) -> list of [n_s, 1, V] fp16 arrays.
         ``score_mode="loglik"``: list of [n_s, 3] float32 arrays (log p(suffix | prefix), its token
         count, 1.0 if every token is the greedy one), per-token values in ``last_token_logprobs``.
+        ``score_mode="embed"``: list of [n_s, D] float32 arrays (embed.py: each suffix's pooled
+        final-norm rows).
         ``score_top_k=K``: list of ``TOPK_DTYPE`` [n_s, 1, K] arrays (the K best (id, probability)
         pairs in rank order, topk.py), the chosen tokens' probabilities in ``last_token_probs``."""
         if self.my_shards and prompts and not self.resume_dir and not self.hip_graphs:
@@ -504,10 +537,33 @@ class ShardedRunner:
                 if min(ids) < 0 or max(ids) >= V:
                     raise ValueError(f"score_mode='loglik': suffix {s} of prompt {i} holds a token id outside [0, {V})")
 
+    def _check_embed(self, tps) -> None:
+        """An embed call, validated on the host before any launch: mean pooling needs a token in
+        every suffix (an empty one has no row to pool)."""
+        if self.embed.pooling != "mean":
+            return
+        for i, tp in enumerate(tps):
+            for s, (ids, e) in enumerate(zip(tp.suffixes, tp.eos_index)):
+                if e < 0 or not ids:
+                    raise ValueError(f"score_mode='embed' with --embed_pooling mean: suffix {s} of prompt {i} "
+                                     "has no token to pool")
+
+    def set_mean_variant(self, pruned: bool) -> None:
+        """Mean pooling: run the last decoder layer unpruned (default; every row computed, the norm
+        gathers the suffix rows) or pruned to the suffix rows (one single-query attention item per
+        suffix row).  The embeddings agree to rounding; profiles/embed/README.md has the timings."""
+        if self.embed is None or self.embed.pooling != "mean":
+            raise ValueError("set_mean_variant needs score_mode='embed' with mean pooling")
+        self._mean_pruned = bool(pruned)
+        self._all_suffix_rows = not pruned
+        self.ctx.prune_last = bool(pruned)
+
     def _check_drafts(self, tps, drafts) -> List[List[int]]:
         """A call with prompt-lookup drafts, validated before any launch -> the rows scored per
         suffix (its last token before the draft, then one per draft token)."""
         V = self.cfg.vocab_size
+        if self.embed is not None:
+            raise ValueError("drafts do not combine with score_mode='embed' (--lookup_decoding)")
         if not self.row_exact:
             raise ValueError("drafts need the prefix K/V cache and exact_reuse (row-exact calls): a verified "
                              "row's scores must be those of the call that computes it alone")
@@ -555,6 +611,13 @@ class ShardedRunner:
             self._check_loglik(tps)
             self._pair_lens = [[len(s) for s in tp.suffixes] for tp in tps]
             self.last_token_logprobs = [None] * n
+        pool = None
+        if self.embed is not None:
+            self._check_embed(tps)
+            pool = self.embed.pooling
+            if self._mean_pruned:
+                # every suffix row is a scored row of the pruned last layer, pooled per suffix
+                score_rows, pool = [[len(s) for s in tp.suffixes] for tp in tps], "last"
         window = self._call_window(tps)
         entry, cached = self._prefix_entry(tps)
         if self._vram_cap:
@@ -577,9 +640,10 @@ class ShardedRunner:
                                 suffix_rows=[sfx_rows[i] for i in g] if sfx_rows is not None else None,
                                 suffix_keep=[sfx_keep[i] for i in g] if sfx_keep is not None else None,
                                 single_suffix_items=self.row_exact, window=window, loglik=self.loglik,
-                                score_rows=[score_rows[i] for i in g] if score_rows is not None else None)
+                                score_rows=[score_rows[i] for i in g] if score_rows is not None else None,
+                                pool=pool)
                    for g in groups]
-        if score_rows is not None:
+        if drafts is not None:
             for b, g in zip(batches, groups):
                 cnt = np.asarray([c for i in g for c in score_rows[i]], dtype=np.int64)
                 b.row_start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
@@ -635,8 +699,10 @@ class ShardedRunner:
                                         weight_bytes=self.prefetcher.planned_hbm_bytes() if self.cuda else None,
                                         fused_norm=self.ctx.fused_norm, extra_bytes=stage,
                                         grouped=self.prefix_cache is None,
-                                        scored_rows=(sum(len(s) for tp in tps for s in tp.suffixes) if self.loglik
-                                                     else scored_rows))
+                                        # (loglik's norm state is a tensor of its own; mean pooling's
+                                        # normed rows live in the arena, a chunk at a time: no charge)
+                                        scored_rows=(sum(len(s) for tp in tps for s in tp.suffixes)
+                                                     if (self.loglik or self._mean_pruned) else scored_rows))
         if self.loglik and self.ctx.ws is not None and (mc, ar, qc) != (self.ctx.mlp_chunk, self.ctx.attn_rows,
                                                                           self.ctx.qkv_chunk):
             # the norm state grows with the call's scored pairs and the plan shrinks the chunks to
@@ -1444,6 +1510,8 @@ class ShardedRunner:
         self.score_d2h_bytes += probs.nbytes + (4 * am.numel() if am is not None else 0)
         if self.loglik:
             return self._collect_loglik(batch, probs, outputs)
+        if self.embed is not None:
+            return self._collect_embed(batch, probs, outputs)
         if self.score_top_k:
             return self._collect_topk(batch, probs, outputs)
         am = am.numpy() if am is not None else None
@@ -1474,6 +1542,16 @@ class ShardedRunner:
                 r += n
             outputs[pid] = out
             self.last_token_logprobs[pid] = per_tok
+
+    def _collect_embed(self, batch: PackedBatch, emb: np.ndarray, outputs) -> None:
+        """The [n_suffixes, D] float32 embeddings of a finished micro-batch (prompt -> suffix order)
+        split back into prompts."""
+        assert emb.dtype == np.float32 and emb.shape == (int(sum(batch.n_suffix)), self.embed.dim), (emb.dtype, emb.shape)
+        r = 0
+        for j, pid in enumerate(batch.prompt_ids):
+            ns = batch.n_suffix[j]
+            outputs[pid] = emb[r:r + ns].copy()
+            r += ns
 
     # ------------------------------------------------- compact scores (score_top_k)
     def _topk_offsets(self, rows: int):
@@ -1659,12 +1737,14 @@ class ShardedRunner:
             ev = torch.cuda.Event()
             ev.record(self.d2h_stream)
             return batch, host, ev, pool_buf, None
-        if self.loglik:
-            am = None                 # probs: the fp32 [n_pairs, 2] head state, copied as it is
+        fp32 = self.loglik or self.embed is not None
+        if fp32:
+            am = None                 # probs: the fp32 [n_pairs, 2] head state (embed: the [n_sfx, D] norm
+            #                           state), copied as it is
         else:
             am = self._pick_rows(batch, probs, self.sample_step) if hasattr(self.ops, "argmax_rows") else None
         if not self.cuda:
-            return batch, probs.detach().to(torch.float32 if self.loglik else torch.float16).cpu(), None, None, am
+            return batch, probs.detach().to(torch.float32 if fp32 else torch.float16).cpu(), None, None, am
         store = self._get_store()
         nbytes = probs.numel() * probs.element_size()
         pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])

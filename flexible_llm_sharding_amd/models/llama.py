@@ -200,6 +200,11 @@ class ExecContext:
     # (0: as many as the arena, or 64 MB, holds)
     loglik: bool = False
     head_chunk: int = 0
+    # pooled embeddings (engine score_mode="embed"; embed.EmbedParams, resolved): the final norm ends
+    # in ops.pool_rows over meta["seg_start"], pool_chunk normed rows at a time (0: as many as the
+    # arena holds); there is no head layer
+    embed: Optional[object] = None
+    pool_chunk: int = 0
     ss_buf: Optional[torch.Tensor] = None      # the arena-backed buffer (grown, reused)
     ss_cur: Optional[torch.Tensor] = None      # the buffer the last residual GEMM wrote
     ss_key: Optional[tuple] = None
@@ -602,10 +607,56 @@ def _shared_expert(ctx: ExecContext, W: Dict[str, torch.Tensor], h: torch.Tensor
     return s * g
 
 
-def run_norm(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, meta: dict) -> torch.Tensor:
+def run_norm(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, meta: dict, batch=None) -> torch.Tensor:
+    if ctx.embed is not None:
+        return _norm_pool(ctx, W, x, meta, batch)
     if ctx.prune_last and ctx.last_decoder:
         return ctx.ops.rmsnorm(x, W["norm"], ctx.cfg.rms_norm_eps)    # rows already gathered
     return ctx.ops.gather_rmsnorm(x, meta["last_idx"], W["norm"], ctx.cfg.rms_norm_eps)
+
+
+def _norm_pool(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, meta: dict, batch) -> torch.Tensor:
+    """The final norm of an embed-mode pass: [n_suffixes, D] fp32 pooled embeddings (embed.py).
+    The normed rows exist one chunk of whole suffixes at a time, in the workspace arena (idle in
+    the norm phase); ``rmsnorm`` and ``pool_rows`` are both per-row / per-suffix, so the chunking
+    does not change a bit of the result."""
+    ops, ep, eps = ctx.ops, ctx.embed, ctx.cfg.rms_norm_eps
+    H = x.shape[1]
+    gathered = bool(ctx.prune_last and ctx.last_decoder)       # x holds the scored rows, in order
+    idx, seg_dev, seg = meta["last_idx"], meta["seg_start"], batch.seg_start
+    n_seg, n_rows = len(seg) - 1, int(seg[-1])
+    out = torch.empty(n_seg, ep.dim, dtype=torch.float32, device=x.device)
+    ws = ctx.ws
+    cap = n_rows
+    if ws is not None and ws.buf is not None:
+        ws.reset()
+        cap = ws.buf.numel() // H
+    if ctx.pool_chunk > 0:
+        cap = min(cap, ctx.pool_chunk)
+    i0 = 0
+    while i0 < n_seg:
+        a = int(seg[i0])
+        i1 = i0 + 1                                  # whole suffixes, at least one
+        while i1 < n_seg and int(seg[i1 + 1]) - a <= cap:
+            i1 += 1
+        b = int(seg[i1])
+        n = b - a
+        scratch = None
+        if ws is not None and ws.buf is not None and n * H <= ws.buf.numel():
+            ws.reset()
+            scratch = ws.take(n, H)
+        rows = None if gathered else idx[a:b]
+        src = x[a:b] if gathered else x
+        if scratch is not None:
+            y = ops.rmsnorm(src, W["norm"], eps, row_idx=rows, out=scratch)
+        elif rows is not None:
+            y = ops.gather_rmsnorm(src, rows, W["norm"], eps)
+        else:
+            y = ops.rmsnorm(src, W["norm"], eps)
+        ss = seg_dev[i0:i1 + 1] if a == 0 else seg_dev[i0:i1 + 1] - a
+        ops.pool_rows(y, ss.contiguous(), ep.dim, ep.normalize, out=out[i0:i1])
+        i0 = i1
+    return out
 
 
 def run_head(ctx: ExecContext, W: Dict[str, torch.Tensor], h: torch.Tensor, meta: Optional[dict] = None) -> torch.Tensor:
@@ -633,7 +684,7 @@ def run_layer(ctx: ExecContext, layer_name: str, W: Dict[str, torch.Tensor],
     if kind == "decoder":
         return run_decoder(ctx, W, state, batch, meta, layer_name)
     if kind == "norm":
-        return run_norm(ctx, W, state, meta)
+        return run_norm(ctx, W, state, meta, batch)
     return run_head(ctx, W, state, meta)
 
 

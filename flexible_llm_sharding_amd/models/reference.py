@@ -142,6 +142,35 @@ def reference_logliks(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompt
     return outs
 
 
+def reference_embeddings(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence,
+                         pooling: str = "last", dim: int = 0, normalize: bool = True,
+                         prefix_attention: str = "bidirectional", max_len: int = 4096,
+                         cos=None, sin=None) -> List[np.ndarray]:
+    """Per prompt a float32 [n_s, D] array: each suffix's pooled final-norm hidden state (embed.py),
+    from the forward of :func:`reference_scores`.  ``pooling="last"``: the final-norm row of the
+    suffix's last real token; ``"mean"``: the mean of the final-norm rows of its real tokens;
+    ``dim`` (0: H): the first D columns; ``normalize``: divided by max(L2 norm, 1e-12)."""
+    if pooling not in ("last", "mean"):
+        raise ValueError(pooling)
+    D = int(dim) or cfg.hidden_size
+    if not 1 <= D <= cfg.hidden_size:
+        raise ValueError(f"dim={dim}")
+    outs = []
+    for P, S, sids, eos in _forward(cfg, sd, tok, prompts, prefix_attention, max_len, cos, sin):
+        Y = _rms(S, sd["model.norm.weight"].float(), cfg.rms_norm_eps)             # [ns, Ls, H]
+        rows = []
+        for s in range(sids.shape[0]):
+            L = int(eos[s]) + 1
+            if L < 1 and pooling == "mean":
+                raise ValueError(f"suffix {s} has no real token")
+            rows.append(Y[s, L - 1] if pooling == "last" else Y[s, :L].mean(0))
+        e = torch.stack(rows)[:, :D]
+        if normalize:
+            e = F.normalize(e, p=2.0, dim=1, eps=1e-12)
+        outs.append(e.numpy().astype(np.float32))
+    return outs
+
+
 def _forward(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence, prefix_attention: str,
              max_len: int, cos, sin):
     """Per prompt: (prefix hidden states [1, Lp, H], suffix hidden states [n_s, Ls, H] after the

@@ -654,6 +654,42 @@ class HipOps:
                 self.logprob_rows(logits, targets[s:s + n], logits_scaling, out=out[s:s + n])
         return out
 
+    def pool_rows(self, x, seg_start, dim: int = 0, normalize: bool = True, row_idx=None, out=None):
+        """[n_seg, D] fp32: per segment the mean over its rows of the first ``D = dim or H`` columns
+        of the fp16 rows ``x`` (embed.py holds the definition and the summation order), optionally
+        L2-normalised.  The row list is ``x[row_idx]`` (int32 CUDA vector) or ``x`` itself; segment i
+        owns entries ``seg_start[i] .. seg_start[i + 1] - 1`` of it (int32 CUDA vector of n_seg + 1
+        non-decreasing entries).  A segment of one row returns that row's bits."""
+        _f16(x, "x")
+        if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            raise TypeError("x must be a [rows, H] tensor with unit column stride and a row stride >= H")
+        n_src, H = x.shape
+        for t, name in ((seg_start, "seg_start"), (row_idx, "row_idx")):
+            if t is None:
+                continue
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise TypeError(f"{name} must be a contiguous int32 CUDA vector")
+            if t.device != x.device:
+                raise TypeError(f"x and {name} must be on one device")
+        if seg_start.numel() < 1:
+            raise TypeError("seg_start needs n_seg + 1 entries")
+        D = int(dim) or H
+        if isinstance(dim, bool) or not 1 <= D <= H:
+            raise ValueError(f"dim in 1..{H} (0: {H}) expected, got {dim!r}")
+        n_seg = seg_start.numel() - 1
+        n_list = row_idx.numel() if row_idx is not None else n_src
+        if out is None:
+            out = torch.empty(n_seg, D, dtype=torch.float32, device=x.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n_seg, D) or not out.is_contiguous():
+            raise TypeError(f"out must be a contiguous fp32 [{n_seg}, {D}] tensor")
+        if n_seg and n_list == 0:
+            return out.zero_()
+        _chk(self.k.fls_pool_rows(x.data_ptr(), x.stride(0), n_src, H,
+                                  row_idx.data_ptr() if row_idx is not None else None, n_list,
+                                  seg_start.data_ptr(), n_seg, D, int(bool(normalize)), out.data_ptr(), _stream()),
+             "fls_pool_rows")
+        return out
+
     def cast_f16(self, dst: torch.Tensor, src: torch.Tensor, src_code: int) -> None:
         """dst (fp16 bytes) = fp16(src bytes of bf16 (code 1; may be in place) or fp32 (code 2))."""
         n = dst.numel() * dst.element_size() // 2

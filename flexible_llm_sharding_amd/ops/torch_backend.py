@@ -233,6 +233,28 @@ class TorchOps:
             out[s:s + step] = self.logprob_rows(logits, targets[s:s + step], logits_scaling)
         return out
 
+    def pool_rows(self, x: torch.Tensor, seg_start: torch.Tensor, dim: int = 0, normalize: bool = True,
+                  row_idx: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
+        """HipOps.pool_rows in fp32 (embed.py's definition): per segment of the row list
+        (``x[row_idx]`` or ``x``) the mean of the first ``dim or H`` columns, optionally divided by
+        max(its L2 norm, 1e-12); an empty segment gives zeros."""
+        H = x.shape[1]
+        D = int(dim) or H
+        if isinstance(dim, bool) or not 1 <= D <= H:
+            raise ValueError(f"dim in 1..{H} (0: {H}) expected, got {dim!r}")
+        rows = x.index_select(0, row_idx.long()) if row_idx is not None else x
+        ss = [int(v) for v in seg_start.tolist()]
+        res = torch.zeros(len(ss) - 1, D, dtype=torch.float32, device=x.device)
+        for i, (a, b) in enumerate(zip(ss[:-1], ss[1:])):
+            if b > a:
+                res[i] = rows[a:b, :D].float().sum(0) / float(b - a)
+        if normalize:
+            res = res / res.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
     def row_exact(self, on: bool = True):
         """HipOps.row_exact: nothing to select here (one matmul path)."""
         import contextlib

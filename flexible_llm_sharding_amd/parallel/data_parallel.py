@@ -324,15 +324,21 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
     from ..runtime.stream import FileLayerSource
     from .planner import make_plan
     device = torch.device(device)
+    from ..embed import EmbedParams, layer_names as mode_layer_names
+    mode = getattr(args, "score_mode", "next_token")
+    names = mode_layer_names(cfg, mode)              # (embed: no lm_head, which need not exist)
+    embed_kw = {}
+    if mode == "embed":
+        ep = EmbedParams.from_args(args)
+        embed_kw = dict(embed_pooling=ep.pooling, embed_dim=ep.dim, embed_normalize=ep.normalize)
     if store is None and getattr(args, "synthetic", None):
         from .. import knobs
         store = SlicedHostStore.synthetic(cfg, device, comm.rank, comm.world, pinned=device.type == "cuda",
                                           fold_norms=device.type == "cuda" and knobs.get_int("FLS_QKV_FOLD") == 1)
     elif store is None:
-        src = FileLayerSource(cfg, args.model_path, direct=getattr(args, "o_direct", False))
+        src = FileLayerSource(cfg, args.model_path, names=names, direct=getattr(args, "o_direct", False))
         store = src if weight_cache == "stream" else SlicedHostStore.from_source(
             src, comm.rank, comm.world, pinned=device.type == "cuda")
-    names = cfg.layer_names()
     plan = make_plan(len(names), args.layer_num_per_shard, comm.world, comm.rank, True)
     shards = [s for s in plan.my_shards if len(s)]
     # the prefetcher's gather communicator (its comm.dup()): torch.distributed, or the native RCCL one
@@ -362,7 +368,7 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None),
-                         score_top_k=int(getattr(args, "score_top_k", 0) or 0))
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), **embed_kw)
 
 
 def _suffix_kv(args, comm: Comm) -> bool:

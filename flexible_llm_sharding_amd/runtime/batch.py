@@ -107,6 +107,8 @@ class PackedBatch:
                                                 # suffix's range of ``last_idx`` ...
     draft: Optional[np.ndarray] = None          # ... and [S_total] int32 the draft token scored next to each
                                                 # scored row, -1 on a suffix's last (ops.verify_rows)
+    seg_start: Optional[np.ndarray] = None      # pooled embeddings (``pack_prompts(pool=...)``): [n_sfx + 1]
+                                                # int32, each suffix's range of ``last_idx`` (ops.pool_rows)
     _dev: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -207,7 +209,7 @@ class PackedBatch:
              "last_idx": self.last_idx, "last_pos": self.positions[self.last_idx].astype(np.int32),
              "work_last": self.work_last}
         for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win",
-                     "r0_lo", "r0_item", "r0_item_last", "targets", "row_start", "draft"):
+                     "r0_lo", "r0_item", "r0_item_last", "targets", "row_start", "draft", "seg_start"):
             v = getattr(self, name)
             if v is not None:
                 m[name] = v
@@ -230,7 +232,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                  suffix_rows: Optional[Sequence[Sequence[int]]] = None,
                  suffix_keep: Optional[Sequence[Sequence[int]]] = None,
                  single_suffix_items: bool = False, window: int = 0, loglik: bool = False,
-                 score_rows: Optional[Sequence[Sequence[int]]] = None) -> PackedBatch:
+                 score_rows: Optional[Sequence[Sequence[int]]] = None, pool: Optional[str] = None) -> PackedBatch:
     """Pack prompts into one token matrix + attention work items.
 
     ``prefix_offsets`` (rows of each prompt's prefix in a PrefixEntry) turns on
@@ -269,7 +271,21 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     ``last_idx``, ``last_segments``, ``work_last`` (one single-query item per scored row, as for
     the last row today) and the pruned last layer's scored set then hold k entries per suffix, in
     row order.  None, or 1 everywhere, is the packing without it, byte for byte.
+
+    ``pool`` (pooled embeddings, embed.py): ``seg_start`` then holds each suffix's range of
+    ``last_idx``, in prompt -> suffix order.  ``"last"``: today's scored rows, one per suffix.
+    With ``score_rows`` (``"last"`` only) a suffix's range covers its k scored rows.
+    ``"mean"``: ``last_idx`` holds every row of every suffix, in row order (``prompt_scored`` ranges
+    over them; ``last_segments`` / ``work_last`` stay per suffix: such a batch runs the unpruned last
+    layer, which reads neither); every suffix needs a token; not with ``kv_cached`` / ``suffix_keep``.
     """
+    if pool not in (None, "last", "mean"):
+        raise ValueError(f"pool={pool!r}")
+    if pool is not None and (loglik or (score_rows is not None and pool != "last")):
+        raise ValueError("pool does not combine with loglik packing, mean pooling not with score_rows")
+    mean = pool == "mean"
+    if mean and (kv_cached or suffix_keep is not None):
+        raise ValueError("mean pooling does not combine with kv_cached / suffix_keep")
     if score_rows is not None and loglik:
         raise ValueError("score_rows does not combine with loglik packing")
     if loglik and (kv_cached or suffix_keep is not None):
@@ -293,13 +309,13 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     r0_lo, r0_item, r0_item_last = [], [], []
     src, dst, sfx_src, sfx_dst = [], [], [], []
     p_rows, p_items, p_scored = [], [], []
-    pair_rows, pair_tgt, n_pairs = [], [], 0       # loglik: (row, target) pairs
+    pair_rows, pair_tgt, n_pairs = [], [], 0       # loglik: (row, target) pairs; mean pooling: suffix rows
     t = 0
     padded = 0
     max_pos = 0
     for j, tp in enumerate(tps):
         Lp = len(tp.prefix)
-        row0, item0, sc0 = t, len(work), (n_pairs if loglik else len(last))
+        row0, item0, sc0 = t, len(work), (n_pairs if (loglik or mean) else len(last))
         if loglik and Lp == 0:
             raise ValueError(f"loglik: prompt {prompt_ids[j]} has no prefix token to score a suffix's first token at")
         if kv_cached:
@@ -353,6 +369,11 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                 pair_rows.append(rows)
                 pair_tgt.append(np.asarray(s, dtype=np.int32))
                 n_pairs += n
+            if mean:
+                if n == 0:
+                    raise ValueError(f"mean pooling: suffix {si} of prompt {prompt_ids[j]} has no token")
+                pair_rows.append(np.arange(s0, s0 + n, dtype=np.int32))
+                n_pairs += n
             # the scored row alone, for a last decoder layer that computes only scored rows (row i of
             # the packed suffix sees the suffix up to itself: one row today, the last)
             for i in range(n - k_sc, n):
@@ -404,7 +425,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         max_pos = max(max_pos, Lp + max([len(s) for s in tp.suffixes] or [0]))
         p_rows.append((row0, t))
         p_items.append((item0, len(work)))
-        p_scored.append((sc0, n_pairs if loglik else len(last)))
+        p_scored.append((sc0, n_pairs if (loglik or mean) else len(last)))
         nsuf.append(tp.n_suffix)
         padded += tp.padded_tokens
     work = np.asarray(work, dtype=np.int32).reshape(-1, WORK_ITEM_FIELDS)
@@ -412,11 +433,16 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
 
     def cat(parts):
         return np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    seg_start = None
+    if pool is not None:
+        cnt = ([len(r) for r in pair_rows] if mean else [int(k) for ks in score_rows for k in ks]
+               if score_rows is not None else [1] * len(last))
+        seg_start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
     return PackedBatch(
         prompt_ids=list(prompt_ids), n_suffix=nsuf,
         ids=cat(ids), positions=cat(pos),
         segments=segs, work=work, seg_lo=cat(seg_lo),
-        last_idx=cat(pair_rows) if loglik else np.asarray(last, dtype=np.int32), last_segments=lsegs,
+        last_idx=cat(pair_rows) if (loglik or mean) else np.asarray(last, dtype=np.int32), last_segments=lsegs,
         work_last=(np.asarray(lwork, dtype=np.int32).reshape(-1, WORK_ITEM_FIELDS) if reuse
                    else _work_items(lsegs)), num_tokens=t, padded_tokens=padded,
         max_pos=max_pos, kv_cached=kv_cached, q_block=q_block,
@@ -434,7 +460,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         r0_lo=cat(r0_lo) if W else None,
         r0_item=np.asarray(r0_item, dtype=np.int32).reshape(-1, 2) if W else None,
         r0_item_last=np.asarray(r0_item_last, dtype=np.int32).reshape(-1, 2) if W else None,
-        targets=cat(pair_tgt) if loglik else None)
+        targets=cat(pair_tgt) if loglik else None, seg_start=seg_start)
 
 
 def _items(sg: Segment, q_block: int = Q_BLOCK) -> List[tuple]:

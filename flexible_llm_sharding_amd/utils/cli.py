@@ -55,13 +55,26 @@ def build_parser() -> argparse.ArgumentParser:
                         "prompt longer than it: error (default) refuses the call; apply runs sliding-window "
                         "attention (a query sees the last sliding_window positions, its own included; calls that "
                         "fit the window run unchanged)")
-    p.add_argument("--score_mode", choices=["next_token", "loglik"], default="next_token",
+    p.add_argument("--score_mode", choices=["next_token", "loglik", "embed"], default="next_token",
                    help="next_token (default): the next-token distribution after each suffix ([n_s, 1, V] fp16 per "
                         "prompt).  loglik: log p(suffix | prefix), summed over the suffix's tokens in one pass "
                         "([n_s, 3] float32 per prompt: the sum, the token count, 1 if every token is the greedy "
                         "one); --output_file then holds the per-token log-probabilities.  Not with --num_gen_token "
                         "> 1, --hip_graphs, --prefix_kv_cache / --suffix_kv_cache true, --resume_dir or model "
-                        "parallel")
+                        "parallel.  embed: each suffix's pooled final-norm hidden state ([n_s, D] float32 per "
+                        "prompt; --embed_pooling, --embed_dim, --embed_normalize); the pass ends at model.norm, so "
+                        "a model directory without lm_head.safetensors runs.  Not with what loglik refuses, nor "
+                        "with --do_sample, --score_top_k or --lookup_decoding")
+    p.add_argument("--embed_pooling", choices=["last", "mean"], default=None,
+                   help="with --score_mode embed: last (default): the final-norm row of the suffix's last token "
+                        "(the row the LM head scores); mean: the fp32 mean of the final-norm rows of the suffix's "
+                        "own tokens (the prefix is not pooled)")
+    p.add_argument("--embed_dim", type=int, default=None, metavar="D",
+                   help="with --score_mode embed: keep the first D columns (Matryoshka truncation); 1 to the hidden "
+                        "size, 0 (default): the hidden size")
+    p.add_argument("--embed_normalize", type=str2bool, nargs="?", const=True, default=None,
+                   help="with --score_mode embed: divide each embedding by max(its L2 norm over the kept "
+                        "columns, 1e-12) (default true)")
     p.add_argument("--do_sample", type=str2bool, nargs="?", const=True, default=False,
                    help="draw every generated token from the next-token distribution instead of taking its "
                         "argmax (temperature, then top-k, then top-p; integer-exact, so device and host draw the "
@@ -178,6 +191,35 @@ def check_score_mode(args) -> None:
             raise ValueError(f"--score_mode loglik does not combine with {flag}")
 
 
+def check_embed(args, hidden_size: int = 0) -> None:
+    """``--score_mode embed`` and the ``--embed_*`` flags: values in range (``--embed_dim`` against
+    ``hidden_size`` once the model is known), no ``--embed_*`` flag without the mode, and none of
+    the modes it is not built for; a ``ValueError`` names the flag."""
+    from ..embed import check_embed_values
+    pooling, dim, norm = (getattr(args, "embed_pooling", None), getattr(args, "embed_dim", None),
+                          getattr(args, "embed_normalize", None))
+    if getattr(args, "score_mode", "next_token") != "embed":
+        for v, flag in ((pooling, "--embed_pooling"), (dim, "--embed_dim"), (norm, "--embed_normalize")):
+            if v is not None:
+                raise ValueError(f"{flag} needs --score_mode embed")
+        return
+    check_embed_values(pooling or "last", dim or 0)
+    if hidden_size and (dim or 0) > hidden_size:
+        raise ValueError(f"--embed_dim must be in 1..{hidden_size} (the hidden size), got {dim}")
+    sampled = (getattr(args, "do_sample", False) or getattr(args, "temperature", 1.0) != 1.0
+               or getattr(args, "top_k", 0) != 0 or getattr(args, "top_p", 1.0) != 1.0)
+    for bad, flag in ((getattr(args, "num_gen_token", 1) != 1, "--num_gen_token other than 1"),
+                      (sampled, "--do_sample (and --temperature / --top_k / --top_p)"),
+                      (getattr(args, "score_top_k", 0), "--score_top_k"),
+                      (getattr(args, "lookup_decoding", 0), "--lookup_decoding"),
+                      (getattr(args, "hip_graphs", False), "--hip_graphs"),
+                      (getattr(args, "prefix_kv_cache", False) is True, "--prefix_kv_cache true"),
+                      (getattr(args, "suffix_kv_cache", False) is True, "--suffix_kv_cache true"),
+                      (getattr(args, "resume_dir", None), "--resume_dir")):
+        if bad:
+            raise ValueError(f"--score_mode embed does not combine with {flag}")
+
+
 def check_sampling(args) -> None:
     """The sampling flags: values in range, no sampling parameter without ``--do_sample``, no
     sampling inside ``--score_mode loglik``; a ``ValueError`` names the flag."""
@@ -237,6 +279,7 @@ def check_lookup(args, world: int = 1) -> None:
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     check_score_mode(args)
+    check_embed(args)
     check_sampling(args)
     check_top_k(args)
     check_lookup(args)

@@ -26,9 +26,17 @@ import torch
 from .safetensors_io import load_file, save_file
 
 
+def canonical_param(name: str) -> str:
+    """The tensor's name in a causal-LM checkpoint.  ``AutoModel.save_pretrained`` (the published
+    embedding checkpoints) writes the bare model's names — ``embed_tokens.weight``, ``layers.N.*``,
+    ``norm.weight`` — which get the ``model.`` prefix here, so their layer files are the usual ones."""
+    return "model." + name if name.startswith(("embed_tokens.", "layers.", "norm.")) else name
+
+
 def layer_of_param(name: str) -> str:
-    """prepare_weights.py:21 — first three dotted components after stripping '.weight'."""
-    return ".".join(name.replace(".weight", "").split(".")[:3])
+    """prepare_weights.py:21 — first three dotted components after stripping '.weight' (of the
+    canonical name: a prefix-less ``layers.0.self_attn.q_proj.weight`` belongs to ``model.layers.0``)."""
+    return ".".join(canonical_param(name).replace(".weight", "").split(".")[:3])
 
 
 def normalize_expert_names(model_type: str, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -105,7 +113,10 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True) -> List[
     layer_params: Dict[str, List[str]] = defaultdict(list)
     for p in wmap:
         layer_params[layer_of_param(p)].append(p)
-    tied = "lm_head" not in layer_params and "model.embed_tokens.weight" in wmap and _tied(src_dir)
+    # (a checkpoint with neither lm_head nor tied embeddings — a bare embedding model — has no head
+    # file: it runs in --score_mode embed only)
+    tied = ("lm_head" not in layer_params and "model.embed_tokens.weight" in {canonical_param(p) for p in wmap}
+            and _tied(src_dir))
     model_type = _config(src_dir).get("model_type", "llama")
     # deterministic order: by the (sorted) source shards each layer needs
     shard_order = {s: i for i, s in enumerate(sorted(set(wmap.values())))}
@@ -132,7 +143,7 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True) -> List[
                 cache[s] = _load_shard(os.path.join(src_dir, s))
         sd = {}
         for p in layer_params[l]:
-            sd[p] = cache[wmap[p]][p]
+            sd[canonical_param(p)] = cache[wmap[p]][p]
         assert len(sd) == len(layer_params[l]), f"Should have {len(layer_params[l])} keys for {l}"
         save_file(normalize_expert_names(model_type, sd), layer_file(out_dir, l))
         written.append(l)
