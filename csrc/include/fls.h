@@ -197,6 +197,17 @@ int fls_pool_rows(const void* x, int ld, int n_src, int H, const int* row_idx, i
                   int n_seg, int D, int normalize, float* out, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
+// weight-only FP8 (OCP e4m3fn) expansion in place (csrc/kernels/dequant.hip; flexible_llm_sharding_amd/fp8.py
+// holds the definition).  region: the tensor's 2n-byte image region (2-byte aligned) whose upper half
+// [n, 2n) holds the n checkpoint bytes; afterwards it holds n fp16 values,
+// w16[i] = fp16_rne(fp32(e4m3fn(b[i])) * scale(i)).  scale (fp32, device): kind 0 one element; kind 1 one
+// per row of `cols` weights; kind 2 one per 128 x 128 block of the [n / cols, cols] tensor, row-major
+// [ceil(rows / 128), ceil(cols / 128)].  Uses no other device memory: fls_dequant_fp8_launches(n)
+// stream-ordered launches on s, the last a single block of at most fls_dequant_fp8_tail() weights.
+// hipErrorInvalidValue for a missing pointer, an odd region address, or n % cols != 0 (kinds 1, 2).
+int fls_dequant_fp8(void* region, uint64_t n, const float* scale, int kind, uint64_t cols, fls_stream_t s);
+int fls_dequant_fp8_launches(uint64_t n);
+int fls_dequant_fp8_tail(void);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0
 int fls_gemv_skinny(const void* x, const void* w, void* c, int M, int N, int K, int ldx, int ldw, int ldc,
                     fls_stream_t s);

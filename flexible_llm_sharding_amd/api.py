@@ -46,7 +46,8 @@ def batch_ranges(n: int, num_batch: int):
     return list(zip([0] + ends[:-1], ends))
 
 
-def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str], sliced: bool) -> str:
+def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str], sliced: bool,
+                         source=None) -> str:
     """``--weight_cache`` -> ``host`` or ``stream``.
 
     ``auto`` pins the packed layers in host RAM only when they fit the host budget
@@ -64,6 +65,11 @@ def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str
     if mode in ("disk", "stream"):
         return "stream"
     need = 0
+    if source is not None and not sliced and source.fp8_tensors():
+        # an FP8 checkpoint is pinned as its file bytes (runtime.weights.CompactHostStore), not as
+        # the fp16 image: a 70B FP8 model asks for about 70 GB instead of 138 GB
+        need = source.file_bytes(names)
+        names = ()
     for n in names:
         lay = layer_layout(cfg, layer_kind(n))
         need += sum(p.chunk for p in piece_slices(lay, comm.world)) if sliced else lay.nbytes
@@ -93,10 +99,31 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device):
     if getattr(args, "synthetic", None):
         return HostStore.synthetic(cfg, device, seed=0, pinned=device.type == "cuda", names=mine, fold_norms=fold)
     src = FileLayerSource(cfg, args.model_path, names=mine, direct=getattr(args, "o_direct", False))
-    if resolve_weight_cache(args, cfg, comm, mine, sliced=False) == "stream":
+    n_fp8 = src.fp8_tensors()
+    if n_fp8 and getattr(args, "verbose", False):
+        print(f"FP8 checkpoint: {n_fp8} e4m3 tensors are expanded to fp16 in HBM (weight-only FP8); "
+              f"{len(src.ignored_scales())} input_scale tensors are ignored: activations stay fp16", file=sys.stderr)
+    if resolve_weight_cache(args, cfg, comm, mine, sliced=False, source=src) == "stream":
         return src
+    if n_fp8:
+        # the files' bytes pinned as they are, FP8 as FP8; norms are folded as each layer lands
+        from .runtime.weights import CompactHostStore
+        return CompactHostStore(src, pinned=device.type == "cuda")
     st = HostStore.from_source(src, pinned=device.type == "cuda", names=mine)
     return st.fold_norms(device) if fold else st
+
+
+def check_fp8_dp_shard(args, cfg: ModelConfig) -> None:
+    """Data-parallel weight sharding streams 1/G byte slices of every layer image, which cut through
+    tensors; an FP8 tensor loads whole (it is expanded in place in its own region), so an FP8
+    checkpoint is refused there.  (``--dp_weight_shard false`` and model parallel load whole
+    layers and are fine.)"""
+    if getattr(args, "synthetic", None) or not getattr(args, "model_path", None):
+        return
+    names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
+    if FileLayerSource(cfg, args.model_path, names=names).fp8_tensors():
+        raise ValueError("--dp_weight_shard true does not serve an FP8 checkpoint (its 1/G byte slices cut through "
+                         "tensors): pass --dp_weight_shard false, or run model parallel")
 
 
 def repeated_passes(args) -> bool:
@@ -216,6 +243,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
         pkv = skv = False
         reserve = 0
     if args.data_parallel and comm.world > 1 and args.dp_weight_shard:
+        check_fp8_dp_shard(args, cfg)
         from .parallel.data_parallel import build_dp_sharded_runner
         hv = getattr(args, "hbm_cache_gb", 0.0)
         if hv not in ("auto", 0, 0.0, None):
@@ -637,6 +665,14 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
         metrics["lookup_decoding"] = int(args.lookup_decoding)
         metrics["lookup_ngram"] = int(getattr(args, "lookup_ngram", 3))
         metrics.update({k: int(v) for k, v in lk.items()})
+    src = runner.src
+    files = getattr(src, "files", src)        # (a compact store wraps its file source)
+    # tensor bytes a pass reads and copies (a packed host store: its images), and how many are FP8
+    metrics["weight_file_bytes"] = int(files.file_bytes() if hasattr(files, "file_bytes")
+                                       else getattr(src, "total_bytes", 0))
+    metrics["fp8_tensors"] = int(files.fp8_tensors()) if hasattr(files, "fp8_tensors") else 0
+    metrics["weight_pinned_bytes"] = int(src.pinned_bytes() if hasattr(src, "pinned_bytes")
+                                         else getattr(src, "total_bytes", 0))
     metrics["score_d2h_bytes_last_pass"] = int(getattr(runner, "score_d2h_bytes", 0))
     if device.type == "cuda":
         metrics["peak_hbm_bytes"] = torch.cuda.max_memory_allocated(device)

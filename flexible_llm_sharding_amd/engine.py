@@ -217,6 +217,10 @@ class ShardedRunner:
         attn_rows = qkv_chunk = 0
         self._outside = None
         self.ops = get_ops(self.dev)
+        if hasattr(source, "prepare_device"):
+            # an FP8 checkpoint's scales go to the device now (one allocation), before any memory is
+            # measured for a VRAM plan
+            source.prepare_device(self.dev)
         # this runner's split-K / split-KV scratch (64 MB): the free tail of the activation arena —
         # split-K only runs for <= 512-row GEMMs, whose phase carves a sliver of an arena sized for
         # the whole micro-batch — or, when the arena is too small, a buffer of its own.  Every

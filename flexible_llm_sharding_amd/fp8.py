@@ -1,0 +1,220 @@
+"""Weight-only FP8 (OCP e4m3fn) checkpoints: the host definition.
+
+A weight stored as the e4m3fn byte ``b`` with the fp32 scale ``s`` of its group has the value
+
+    w16 = fp16_rne( fp32(e4m3fn(b)) * fp32(s) )
+
+one fp32 multiply, then one round-to-nearest-even to fp16 (overflow to +-inf, like torch's
+``.to(float16)``).  e4m3fn: bias 7, no infinities, ``0x7F`` / ``0xFF`` are NaN, max 448; every
+value is exact in fp16 and fp32, so ``fp32(e4m3fn(b))`` is a 256-entry table (:func:`table`).
+
+The scale element of weight ``[r, c]`` of an ``[out, in]`` tensor:
+
+    per tensor          scale ``[]`` / ``[1]``                      the only one
+    per output channel  scale ``[out]`` / ``[out, 1]``               ``r``
+    128 x 128 blocks    scale ``[ceil(out/128), ceil(in/128)]``      ``[r // 128, c // 128]``
+
+bf16 / fp16 scales are widened to fp32 exactly.  Checkpoint conventions, for ``X.weight`` of
+safetensors dtype ``F8_E4M3``: ``X.weight_scale`` (tensor / channel: compressed-tensors),
+``X.weight_scale_inv`` (blocks; a multiplier despite its name: Qwen3-FP8, DeepSeek);
+``X.input_scale`` is ignored (activations stay fp16).
+
+The *fp16 twin* of an FP8 checkpoint is the same directory with every FP8 tensor replaced by its
+``w16`` and the scale tensors removed (:func:`write_twin`): a run on an FP8 checkpoint gives, bit
+for bit, the outputs of the same run on its twin.  The HIP kernel (``csrc/kernels/dequant.hip``)
+computes the same function in place in the HBM weight slot.
+"""
+from __future__ import annotations
+
+import glob
+import os
+import re
+import shutil
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+
+FP8_DTYPE = torch.float8_e4m3fn
+BLOCK = 128
+FP8_MAX = 448.0
+KIND_TENSOR, KIND_CHANNEL, KIND_BLOCK = 0, 1, 2
+KIND_NAMES = {"tensor": KIND_TENSOR, "channel": KIND_CHANNEL, "block128": KIND_BLOCK}
+SCALE_SUFFIXES = ("_scale", "_scale_inv")          # after "X.weight"
+
+_table: Optional[torch.Tensor] = None
+
+
+def table() -> torch.Tensor:
+    """fp32 value of every e4m3fn bit pattern ([256] float32; 0x7F and 0xFF are NaN)."""
+    global _table
+    if _table is None:
+        _table = torch.arange(256, dtype=torch.int16).to(torch.uint8).view(FP8_DTYPE).to(torch.float32)
+    return _table
+
+
+def _ceil_div(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def scale_kind(scale_shape: Sequence[int], weight_shape: Sequence[int]) -> int:
+    """Which of the three scale kinds ``scale_shape`` is for a 2-D weight; ValueError if none."""
+    ss, ws = tuple(scale_shape), tuple(weight_shape)
+    if len(ws) != 2:
+        raise ValueError(f"FP8 weights are 2-D, got shape {ws}")
+    n = 1
+    for s in ss:
+        n *= s
+    if n == 1 and len(ss) <= 2:
+        return KIND_TENSOR          # (one element: the three kinds coincide)
+    if ss in ((ws[0],), (ws[0], 1)):
+        return KIND_CHANNEL
+    if ss == (_ceil_div(ws[0], BLOCK), _ceil_div(ws[1], BLOCK)):
+        return KIND_BLOCK
+    raise ValueError(f"scale shape {ss} fits no scale kind of a {ws} weight")
+
+
+def expand_scale(scale: torch.Tensor, weight_shape: Sequence[int]) -> torch.Tensor:
+    """The fp32 scale of every weight element (broadcastable to ``weight_shape``)."""
+    out, inn = weight_shape
+    s = scale.detach().to("cpu").to(torch.float32)
+    kind = scale_kind(tuple(scale.shape), weight_shape)
+    if kind == KIND_TENSOR:
+        return s.reshape(1, 1)
+    if kind == KIND_CHANNEL:
+        return s.reshape(out, 1)
+    return s.repeat_interleave(BLOCK, 0)[:out].repeat_interleave(BLOCK, 1)[:, :inn]
+
+
+def dequantize(bits: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``w16`` of an ``[out, in]`` tensor of e4m3fn bytes (uint8 or float8_e4m3fn) and its scale."""
+    b = bits.detach().to("cpu")
+    if b.dtype == FP8_DTYPE:
+        b = b.view(torch.uint8)
+    if b.dtype != torch.uint8:
+        raise TypeError(f"FP8 bits are uint8 / float8_e4m3fn, got {b.dtype}")
+    if b.dim() != 2:
+        raise ValueError(f"FP8 weights are 2-D, got shape {tuple(b.shape)}")
+    v = table()[b.to(torch.int64)]
+    return (v * expand_scale(scale, tuple(b.shape))).to(torch.float16)
+
+
+def quantize(w: torch.Tensor, kind: str = "channel") -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(bits float8_e4m3fn [out, in], scale fp32)``: ``scale = amax / 448`` over the scale's group
+    (1 where amax is 0), ``bits = (w.float() / scale).to(float8_e4m3fn)``.  Scale shapes:
+    ``[out, 1]`` (channel), ``[1]`` (tensor), ``[ceil(out/128), ceil(in/128)]`` (block128)."""
+    if kind not in KIND_NAMES:
+        raise ValueError(f"--fp8_scale {kind!r}: one of {sorted(KIND_NAMES)}")
+    if w.dim() != 2:
+        raise ValueError(f"FP8 weights are 2-D, got shape {tuple(w.shape)}")
+    f = w.detach().to("cpu").to(torch.float32)
+    out, inn = f.shape
+    a = f.abs()
+    if kind == "channel":
+        amax = a.amax(1, keepdim=True)
+    elif kind == "tensor":
+        amax = a.amax().reshape(1)
+    else:
+        nb0, nb1 = _ceil_div(out, BLOCK), _ceil_div(inn, BLOCK)
+        pad = torch.zeros(nb0 * BLOCK, nb1 * BLOCK)
+        pad[:out, :inn] = a
+        amax = pad.reshape(nb0, BLOCK, nb1, BLOCK).amax((1, 3))
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    bits = (f / expand_scale(scale, (out, inn))).to(FP8_DTYPE)
+    return bits, scale
+
+
+# --------------------------------------------------------------------------- converter
+# the 2-D projection weights of decoder layers: q/k/v/o, gate/up/down, Phi-3's fused tensors, and
+# expert weights (the shared expert's too).  The router, norms, biases, the shared-expert gate, the
+# embedding and the head stay as they are.
+_QUANTIZED = re.compile(
+    r"^model\.layers\.\d+\.(self_attn\.(q|k|v|o|qkv)_proj|mlp\.(gate|up|down|gate_up)_proj"
+    r"|mlp\.shared_expert\.(gate|up|down)_proj|mlp\.experts\.\d+\.(gate|up|down)_proj"
+    r"|block_sparse_moe\.experts\.\d+\.w[123])\.weight$")
+
+
+def is_quantized_name(name: str) -> bool:
+    """``prepare_weights.py --quantize fp8`` quantises this tensor."""
+    return _QUANTIZED.match(name) is not None
+
+
+def quantize_state_dict(sd: Dict[str, torch.Tensor], kind: str = "channel") -> Dict[str, torch.Tensor]:
+    """``--quantize fp8`` of one file's tensors: every 2-D projection weight (:func:`is_quantized_name`)
+    that is not FP8 already becomes e4m3fn bits plus an fp32 scale, ``X.weight_scale`` for channel /
+    tensor scales and ``X.weight_scale_inv`` for 128 x 128 blocks; everything else passes through."""
+    out = {}
+    for k, v in sd.items():
+        if is_quantized_name(k) and v.dim() == 2 and v.dtype in (torch.float16, torch.bfloat16, torch.float32):
+            bits, scale = quantize(v, kind)
+            out[k] = bits
+            out[k + ("_scale_inv" if kind == "block128" else "_scale")] = scale
+        else:
+            out[k] = v
+    return out
+
+
+# ------------------------------------------------------------------ checkpoint conventions
+def is_scale_name(name: str) -> bool:
+    """A tensor that belongs to an FP8 weight (its scale, or the ignored activation scale)."""
+    return name.endswith((".weight_scale", ".weight_scale_inv", ".input_scale"))
+
+
+def weight_of_scale(name: str) -> str:
+    """``X.weight`` for ``X.weight_scale`` / ``X.weight_scale_inv`` / ``X.input_scale``."""
+    for suf in (".weight_scale_inv", ".weight_scale", ".input_scale"):
+        if name.endswith(suf):
+            return name[:-len(suf)] + ".weight"
+    raise ValueError(name)
+
+
+def find_scale(weight_name: str, available, where: str = "") -> str:
+    """Name of the scale tensor of FP8 tensor ``weight_name`` among ``available``; TypeError naming
+    the tensor and the dtype when there is none, or both."""
+    got = [weight_name + suf for suf in SCALE_SUFFIXES if weight_name + suf in available]
+    if len(got) != 1:
+        what = "has no scale tensor" if not got else "has both weight_scale and weight_scale_inv"
+        raise TypeError(f"{where}{weight_name} (F8_E4M3) {what}")
+    return got[0]
+
+
+def check_scale(weight_name: str, scale_name: str, scale_shape, weight_shape, where: str = "") -> int:
+    """Scale kind of a checkpoint's scale tensor under its naming convention; TypeError otherwise."""
+    try:
+        kind = scale_kind(scale_shape, weight_shape)
+    except ValueError as e:
+        raise TypeError(f"{where}{weight_name} (F8_E4M3): {scale_name} {e}") from None
+    inv = scale_name.endswith("_scale_inv")
+    if kind != KIND_TENSOR and inv != (kind == KIND_BLOCK):
+        want = "128x128 blocks" if inv else "per tensor or per output channel"
+        raise TypeError(f"{where}{weight_name} (F8_E4M3): {scale_name} of shape {tuple(scale_shape)} is not {want}")
+    return kind
+
+
+def dequantize_state_dict(sd: Dict[str, torch.Tensor], where: str = "") -> Dict[str, torch.Tensor]:
+    """The twin of one file's tensors: FP8 tensors -> ``w16``, scale tensors dropped."""
+    out = {}
+    for k, v in sd.items():
+        if is_scale_name(k) and weight_of_scale(k) in sd and sd[weight_of_scale(k)].dtype == FP8_DTYPE:
+            continue
+        if v.dtype == FP8_DTYPE:
+            sk = find_scale(k, sd, where)
+            check_scale(k, sk, tuple(sd[sk].shape), tuple(v.shape), where)
+            out[k] = dequantize(v, sd[sk])
+        else:
+            out[k] = v
+    return out
+
+
+def write_twin(src_dir: str, dst_dir: str) -> None:
+    """Write the fp16 twin of the checkpoint directory ``src_dir`` (per-layer files or an HF
+    directory of safetensors files) to ``dst_dir``."""
+    from .utils.safetensors_io import load_file, save_file
+    os.makedirs(dst_dir, exist_ok=True)
+    for fn in sorted(glob.glob(os.path.join(src_dir, "*"))):
+        base = os.path.basename(fn)
+        if os.path.isdir(fn):
+            continue
+        if base.endswith(".safetensors"):
+            save_file(dequantize_state_dict(load_file(fn), base + ": "), os.path.join(dst_dir, base))
+        else:
+            shutil.copy(fn, os.path.join(dst_dir, base))

@@ -274,8 +274,11 @@ def check_layer_tensors(cfg: ModelConfig, layer_name: str, available) -> None:
     from ..config import SUPPORTED_MODEL_TYPES
     if cfg.model_type in SUPPORTED_MODEL_TYPES:
         return
+    from ..fp8 import is_scale_name, weight_of_scale
     want = {pl.hf_name for pl in placements(cfg, layer_name)}
-    extra = sorted(k for k in available if k not in want and not k.endswith("rotary_emb.inv_freq"))
+    # (the scale tensors of an FP8 checkpoint follow their weight: fp8.py)
+    extra = sorted(k for k in available if k not in want and not k.endswith("rotary_emb.inv_freq")
+                   and not (is_scale_name(k) and weight_of_scale(k) in want))
     if extra:
         raise NotImplementedError(f"model_type={cfg.model_type!r} runs as Llama, but {layer_name} holds tensors a "
                                   f"Llama layer does not have: {extra[:4]}")
@@ -309,6 +312,11 @@ def pack_layer(cfg: ModelConfig, layer_name: str, sd: Dict[str, torch.Tensor],
         t = sd[key]
         if tuple(t.shape) != pl.shape:
             raise ValueError(f"{layer_name}: {key} has shape {tuple(t.shape)}, config expects {pl.shape}")
+        if t.dtype == torch.float8_e4m3fn:
+            from .. import fp8              # weight-only FP8: the image holds w16 (fp8.py)
+            sk = fp8.find_scale(key, sd, f"{layer_name}: ")
+            fp8.check_scale(key, sk, tuple(sd[sk].shape), pl.shape, f"{layer_name}: ")
+            t = fp8.dequantize(t, sd[sk])
         b[pl.offset:pl.offset + pl.nbytes].view(dtype).copy_(t.reshape(-1).to(dtype))
     return out
 

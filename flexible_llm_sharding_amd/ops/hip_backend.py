@@ -695,6 +695,21 @@ class HipOps:
         n = dst.numel() * dst.element_size() // 2
         _chk(self.k.fls_cast_f16(dst.data_ptr(), src.data_ptr(), src_code, n, _stream()), "fls_cast_f16")
 
+    def dequant_fp8(self, region: torch.Tensor, numel: int, scale: torch.Tensor, kind: int, cols: int) -> None:
+        """Expand the ``numel`` e4m3fn bytes in the upper half of the ``2 * numel``-byte ``region`` to
+        fp16 in place (fp8.py's definition; csrc/kernels/dequant.hip).  ``scale``: fp32 on the device,
+        ``kind`` 0 tensor / 1 channel / 2 block128 of the ``[numel / cols, cols]`` tensor."""
+        if region.numel() * region.element_size() != 2 * numel or not region.is_contiguous():
+            raise ValueError("the region of an FP8 tensor is 2 bytes per weight")
+        if scale.dtype != torch.float32 or scale.device != region.device or not scale.is_contiguous():
+            raise TypeError("FP8 scales are contiguous fp32 on the region's device")
+        rows = numel // cols if cols else 0
+        want = 1 if kind == 0 else rows if kind == 1 else -(-rows // 128) * -(-cols // 128)
+        if cols <= 0 or rows * cols != numel or scale.numel() != want:
+            raise ValueError(f"FP8 scale of {scale.numel()} elements does not fit kind {kind} of [{rows}, {cols}]")
+        _chk(self.k.fls_dequant_fp8(region.data_ptr(), numel, scale.data_ptr(), kind, cols, _stream()),
+             "fls_dequant_fp8")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -326,6 +326,25 @@ class TorchOps:
     def synchronize(self):
         pass
 
+    def dequant_fp8(self, region: torch.Tensor, numel: int, scale: torch.Tensor, kind: int, cols: int) -> None:
+        """The ``numel`` e4m3fn bytes in the upper half of the ``2 * numel``-byte ``region`` -> fp16 in
+        place, by the host definition (fp8.dequantize).  ``scale``: flat fp32 of ``kind`` 0 tensor /
+        1 channel / 2 block128 of the ``[numel / cols, cols]`` tensor."""
+        from .. import fp8
+        b = region.view(torch.uint8)
+        if b.numel() != 2 * numel:
+            raise ValueError("the region of an FP8 tensor is 2 bytes per weight")
+        rows = numel // cols
+        s = scale.detach().to("cpu").reshape(-1)
+        if kind == fp8.KIND_CHANNEL:
+            s = s.reshape(rows, 1)
+        elif kind == fp8.KIND_BLOCK:
+            s = s.reshape(-(-rows // fp8.BLOCK), -(-cols // fp8.BLOCK))
+        else:
+            s = s.reshape(1)
+        w = fp8.dequantize(b[numel:].to("cpu").clone().view(rows, cols), s)
+        b.view(torch.float16).copy_(w.reshape(-1))
+
     # ------------------------------------------------------- synthetic init
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         """Random-init one packed layer in place (norm weights ~ 1, embeddings ~ N(0,1))."""

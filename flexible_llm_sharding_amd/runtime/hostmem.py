@@ -171,7 +171,7 @@ def read_header_native(path: str):
             if rc != 0:
                 raise ValueError(f"{path}: bad entry {i} ({rc})")
             nm = name.value.decode()
-            out[nm] = safetensors_io.TensorInfo(nm, safetensors_io.DTYPES[dt.value.decode()],
+            out[nm] = safetensors_io.TensorInfo(nm, safetensors_io.dtype_of(dt.value.decode(), nm, path),
                                                 tuple(shape[:nd.value]), b.value, e.value)
         return out
     finally:

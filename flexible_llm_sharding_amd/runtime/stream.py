@@ -18,7 +18,11 @@ Here the same small-RAM envelope costs no CPU work per pass:
   stream, so disk reads, PCIe DMA and compute of the previous shard overlap;
 * bf16 tensors are converted to fp16 in place in HBM by a HIP kernel on the
   copy stream (``fls_cast_f16``); fp32 tensors (norm weights of mixed
-  checkpoints) are converted on the host while they sit in the pinned chunk.
+  checkpoints) are converted on the host while they sit in the pinned chunk;
+* FP8 (e4m3fn) tensors of a weight-only FP8 checkpoint (:mod:`..fp8`) are read and copied as
+  they are, one byte per weight, into the upper half of the tensor's own region of the image,
+  and expanded to fp16 in place there by ``fls_dequant_fp8`` on the copy stream, scaled by the
+  tensor's scales (read once at plan time, resident on the device in one arena per source).
 
 Data-parallel ranks stream only their 1/G byte range of the packed image
 (:meth:`LayerPlan.pieces`) and complete the layer with an RCCL all-gather
@@ -31,12 +35,12 @@ import ctypes
 import os
 import threading
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, knobs
+from .. import _native, fp8, knobs
 from ..config import ModelConfig
 from ..models.layout import check_layer_tensors, layer_kind, layer_layout, placements, source_key
 from ..utils.layer_format import layer_file
@@ -45,22 +49,39 @@ from . import hostmem
 from .weights import LayerSource
 
 KIND_RAW, KIND_F32 = 0, 1
-_SRC_ES = {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4}
+_SRC_ES = {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, fp8.FP8_DTYPE: 1}
 
 
 @dataclass(frozen=True)
 class TensorRun:
     """One checkpoint tensor: file bytes [file_off, file_off + numel * src_es) -> image bytes
-    [img_off, img_off + 2 * numel)."""
+    [img_off, img_off + 2 * numel).
+
+    An FP8 tensor (``src_es`` 1, weight-only FP8: :mod:`..fp8`) lands as raw bytes in the upper
+    half ``[img_off + numel, img_off + 2 * numel)`` of its region and is expanded to fp16 in place
+    there; ``scale`` is its flat fp32 scale (read at plan time), ``scale_kind`` one of
+    ``fp8.KIND_*``, ``cols`` the tensor's row length."""
     hf_name: str
     file_off: int
     img_off: int
     numel: int
     src_dtype: torch.dtype
+    scale_kind: int = -1
+    cols: int = 0
+    scale: Optional[torch.Tensor] = field(default=None, compare=False, repr=False)
 
     @property
     def src_es(self) -> int:
         return _SRC_ES[self.src_dtype]
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.src_dtype == fp8.FP8_DTYPE
+
+    @property
+    def land_off(self) -> int:
+        """Image offset where the tensor's file bytes land."""
+        return self.img_off + (self.numel if self.is_fp8 else 0)
 
 
 class LayerPlan:
@@ -80,15 +101,38 @@ class LayerPlan:
             if ti.dtype == torch.int8:
                 raise AssertionError("int8 not supported (need to add fp16_statistics)")   # utils.py:129
             if ti.dtype not in _SRC_ES:
-                raise TypeError(f"{path}: {key} has dtype {ti.dtype}; fp16 / bf16 / fp32 supported")
+                raise TypeError(f"{path}: {key} has dtype {ti.dtype}; fp16 / bf16 / fp32 and FP8 (e4m3fn, "
+                                "with a scale tensor) supported")
             if tuple(ti.shape) != pl.shape:
                 raise ValueError(f"{path}: {key} has shape {tuple(ti.shape)}, config expects {pl.shape}")
             if ti.nbytes != pl.numel * _SRC_ES[ti.dtype]:
                 raise ValueError(f"{path}: {key} byte size {ti.nbytes} does not match its shape")
-            runs.append(TensorRun(key, ti.begin, pl.offset, pl.numel, ti.dtype))
+            if ti.dtype == fp8.FP8_DTYPE:
+                runs.append(self._fp8_run(path, key, ti, pl, infos))
+            else:
+                runs.append(TensorRun(key, ti.begin, pl.offset, pl.numel, ti.dtype))
         self.runs = sorted(runs, key=lambda r: r.file_off)
         self.nbytes = layer_layout(cfg, layer_kind(layer_name)).nbytes
+        # bytes of the file's tensors that a pass reads and copies (FP8 tensors: 1 per weight)
         self.file_bytes = sum(r.numel * r.src_es for r in self.runs)
+        self.fp8_tensors = sum(1 for r in self.runs if r.is_fp8)
+        self.ignored_scales = sorted(k for k in infos if k.endswith(".input_scale"))
+
+    @staticmethod
+    def _fp8_run(path: str, key: str, ti: TensorInfo, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
+        """The run of FP8 tensor ``key``: its scale tensor is read now and kept as fp32 on the host."""
+        where = f"{path}: "
+        if len(pl.shape) != 2:
+            raise TypeError(f"{where}{key} has dtype F8_E4M3; only 2-D projection weights may be FP8")
+        sk = fp8.find_scale(key, infos, where)
+        si = infos[sk]
+        kind = fp8.check_scale(key, sk, tuple(si.shape), pl.shape, where)
+        if si.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"{where}{sk} has dtype {si.dtype}; FP8 scales are fp32 / fp16 / bf16")
+        raw = torch.empty(si.nbytes, dtype=torch.uint8)
+        hostmem.pread_into(path, si.begin, si.nbytes, raw)
+        scale = raw.view(si.dtype).to(torch.float32).reshape(-1).contiguous()
+        return TensorRun(key, ti.begin, pl.offset, pl.numel, ti.dtype, kind, pl.shape[1], scale)
 
     def pieces(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
         """(file_off, file_bytes, dst_off, kind) covering image bytes [lo, hi); dst_off relative to lo.
@@ -100,6 +144,12 @@ class LayerPlan:
         for r in self.runs:
             a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
             if a >= b:
+                continue
+            if r.is_fp8:
+                if (a, b) != (r.img_off, r.img_off + 2 * r.numel):
+                    raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the FP8 tensor "
+                                     f"{r.hf_name} (an FP8 tensor loads whole)")
+                out.append((r.file_off, r.numel, r.land_off - lo, KIND_RAW))
                 continue
             e0, e1 = (a - r.img_off) // 2, (b - r.img_off) // 2
             out.append((r.file_off + e0 * r.src_es, (e1 - e0) * r.src_es, a - lo,
@@ -118,6 +168,13 @@ class LayerPlan:
             if a < b:
                 out.append((a - lo, b - a))
         return out
+
+    def fp8_runs(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, TensorRun]]:
+        """(region offset relative to lo, run) of the FP8 tensors within [lo, hi): expanded to fp16 in
+        place after landing."""
+        hi = self.nbytes if hi is None else hi
+        return [(r.img_off - lo, r) for r in self.runs
+                if r.is_fp8 and r.img_off >= lo and r.img_off + 2 * r.numel <= hi]
 
 
 def _relabel_layer(infos: Dict[str, TensorInfo], layer_name: str) -> Dict[str, TensorInfo]:
@@ -166,6 +223,9 @@ class FileLayerSource(LayerSource):
         self._lock = threading.Lock()
         self._streamer = None
         self._streamer_dev = None
+        self._scale_arena: Optional[torch.Tensor] = None     # FP8 scales on the device (prepare_device)
+        self._scales: Optional[Dict[Tuple[str, str], torch.Tensor]] = None
+        self._scales_dev = None
         self.read_seconds = 0.0
         self.read_bytes = 0
 
@@ -200,6 +260,10 @@ class FileLayerSource(LayerSource):
         for off, nb in pl.bf16_runs(lo, hi):
             v = b[off:off + nb]
             v.view(torch.float16).copy_(v.view(torch.bfloat16).clone())
+        for off, r in pl.fp8_runs(lo, hi):
+            # FP8 bytes landed in the upper half of the tensor's region: the host definition
+            from ..ops import get_ops
+            get_ops(torch.device("cpu")).dequant_fp8(b[off:off + 2 * r.numel], r.numel, r.scale, r.scale_kind, r.cols)
         self.read_bytes += sum(p[1] for p in pieces)
         self.read_seconds += time.perf_counter() - t0
 
@@ -253,7 +317,9 @@ class FileLayerSource(LayerSource):
         if r < 0:
             raise IOError(f"{pl.path}: streaming failed ({r})")
         self.read_seconds += time.perf_counter() - t0
-        self.read_bytes += int(r)
+        # tensor bytes, as on the host path (the streamer also reads through the small gaps between
+        # two pieces of a file, such as an FP8 checkpoint's scale tensors: its own count is `r`)
+        self.read_bytes += sum(p[1] for p in pieces)
         if cast:
             self.cast_on_gpu(name, dst, lo, hi)
         return int(r)
@@ -261,14 +327,72 @@ class FileLayerSource(LayerSource):
     def cast_on_gpu(self, name: str, dst: torch.Tensor, lo: int = 0, hi: Optional[int] = None) -> None:
         """In-place bf16 -> fp16 of the bf16 tensors in image bytes [lo, hi) of ``dst``, whose byte 0
         is image byte ``lo`` (current stream)."""
-        runs = self.plan(name).bf16_runs(lo, hi)
-        if not runs:
+        pl = self.plan(name)
+        runs, f8 = pl.bf16_runs(lo, hi), pl.fp8_runs(lo, hi)
+        if not runs and not f8:
             return
         from ..ops import get_ops
         ops = get_ops(dst.device)
         for off, nb in runs:
             v = dst[off:off + nb]
             ops.cast_f16(v, v, 1)
+        if f8:
+            # FP8 tensors: expanded to fp16 in place in their own regions (csrc/kernels/dequant.hip)
+            scales = self.prepare_device(dst.device)
+            for off, r in f8:
+                ops.dequant_fp8(dst[off:off + 2 * r.numel], r.numel, scales[(name, r.hf_name)], r.scale_kind, r.cols)
+
+    # ------------------------------------------------------------ FP8 scales
+    def prepare_device(self, device) -> Dict[Tuple[str, str], torch.Tensor]:
+        """The device-resident scale arena: the fp32 scales of every FP8 tensor of this source's
+        layers in ONE allocation, filled when the source first sees the device (the runner calls
+        this before it plans its VRAM, so a cap sees the arena in the measured context).  Returns
+        {(layer, tensor name): fp32 view}."""
+        device = torch.device(device)
+        with self._lock:
+            if self._scales is not None and self._scales_dev == device:
+                return self._scales
+        if self._scales is not None and self._scales_dev != device:
+            raise RuntimeError("one streaming source serves one device")
+        parts, index, off = [], {}, 0
+        for n in self.names:
+            for r in self.plan(n).runs:
+                if r.is_fp8:
+                    cnt = r.scale.numel()
+                    index[(n, r.hf_name)] = (off, cnt)
+                    parts.append(r.scale)
+                    pad = -cnt % 4                 # every scale vector 16-byte aligned
+                    if pad:
+                        parts.append(torch.zeros(pad, dtype=torch.float32))
+                    off += cnt + pad
+        views: Dict[Tuple[str, str], torch.Tensor] = {}
+        arena = None
+        if parts:
+            host = torch.cat(parts)
+            if device.type == "cuda":
+                arena = hostmem.alloc_device(host.numel() * 4, device).view(torch.float32)
+                arena.copy_(host)
+                torch.cuda.current_stream(device).synchronize()
+            else:
+                arena = host
+            views = {k: arena[o:o + c] for k, (o, c) in index.items()}
+        with self._lock:
+            self._scale_arena, self._scales, self._scales_dev = arena, views, device
+        return views
+
+    def scale_arena_bytes(self) -> int:
+        return 0 if self._scale_arena is None else self._scale_arena.numel() * 4
+
+    def fp8_tensors(self) -> int:
+        """FP8 tensors among this source's layers (0: a pure fp16 / bf16 / fp32 checkpoint)."""
+        return sum(self.plan(n).fp8_tensors for n in self.names)
+
+    def file_bytes(self, names: Optional[Sequence[str]] = None) -> int:
+        """Tensor bytes of the layer files (what a pass reads and copies)."""
+        return sum(self.plan(n).file_bytes for n in (self.names if names is None else names))
+
+    def ignored_scales(self) -> List[str]:
+        return [k for n in self.names for k in self.plan(n).ignored_scales]
 
     def stats(self) -> Dict[str, float]:
         out = {"read_s": self.read_seconds, "read_bytes": float(self.read_bytes)}
@@ -286,6 +410,7 @@ class FileLayerSource(LayerSource):
         if self._streamer is not None:
             _native.runtime().fls_streamer_destroy(self._streamer)
             self._streamer = None
+        self._scale_arena = self._scales = self._scales_dev = None
 
     def __del__(self):
         try:

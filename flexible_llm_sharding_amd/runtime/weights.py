@@ -15,6 +15,9 @@ Here a source yields the *packed* layer image (see :mod:`..models.layout`):
   (read once), so each shard H2D is one DMA at PCIe line rate
   (``--weight_cache host``).  Also built directly from synthetic random-init
   weights (generated on the GPU and copied down) for the 70B benchmark.
+* :class:`CompactHostStore` — an FP8 checkpoint's file bytes resident in pinned
+  host memory, FP8 as FP8 (half the RAM and PCIe bytes), copied tensor by tensor
+  to their landing positions and expanded to fp16 in the HBM slot (:mod:`..fp8`).
 * data-parallel scatter-load (:func:`piece_slices`): a rank keeps only its
   1/G byte-slice of every layer piece; the layer (or one piece of it) is
   re-assembled in HBM with an RCCL all-gather over xGMI
@@ -22,11 +25,13 @@ Here a source yields the *packed* layer image (see :mod:`..models.layout`):
 """
 from __future__ import annotations
 
+import ctypes
 import threading
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
+from .. import _native
 from ..config import ModelConfig
 from ..models.layout import LayerLayout, layer_kind, layer_layout
 from . import hostmem
@@ -183,6 +188,115 @@ class HostStore(LayerSource):
         del stage
         st.norms_folded = bool(fold_norms)
         return st
+
+
+class CompactHostStore(LayerSource):
+    """The layer files' tensor bytes resident in pinned host memory as they are in the files —
+    FP8 tensors as FP8, one byte per weight (``--weight_cache host`` for an FP8 checkpoint: half the
+    pinned RAM and half the PCIe bytes of the fp16 image).
+
+    It is a streaming source for the prefetchers (``host_buffer()`` is None): ``stream_into``
+    copies every tensor of the range to its landing position in the HBM slot with one async H2D
+    from pinned memory, and ``cast_on_gpu`` expands the FP8 tensors (and casts bf16 ones) in place
+    as the file source does.  Per layer the tensors sit in file order, each at a
+    ``COMPACT_ALIGN``-byte aligned offset; fp32 tensors are kept as fp16.  ``norms_folded`` stays
+    False: norms cannot be folded into FP8 bytes without requantising, so they are folded as each
+    layer lands."""
+
+    norms_folded = False
+    COMPACT_ALIGN = 16
+
+    def __init__(self, files, pinned: bool = True, threads: int = 4):
+        from . import stream as st
+        self.files, self.cfg, self.dtype = files, files.cfg, files.dtype
+        self.names, self.pinned = list(files.names), pinned
+        self.buffers: Dict[str, torch.Tensor] = {}
+        self._offsets: Dict[str, Dict[str, int]] = {}
+        self.h2d_bytes = 0
+        rt = _native.runtime_or_none()
+        for n in self.names:
+            pl = files.plan(n)
+            offs, off, pieces = {}, 0, []
+            for r in pl.runs:
+                offs[r.hf_name] = off
+                f32 = r.src_dtype == torch.float32
+                pieces.append((r.file_off, r.numel * r.src_es, off, st.KIND_F32 if f32 else st.KIND_RAW))
+                off += self._aligned(r.numel * (2 if f32 else r.src_es))
+            buf = hostmem.alloc_host(off, pinned=pinned)
+            if rt is not None and pieces:
+                arr = st._piece_array(pieces)
+                rc = rt.fls_stream_read_host(pl.path.encode(), ctypes.addressof(arr), len(pieces), buf.data_ptr(),
+                                             max(1, threads))
+                if rc < 0:
+                    raise IOError(f"{pl.path}: read failed ({rc})")
+            else:
+                files._read_pieces_py(pl.path, pieces, buf)
+            self.buffers[n], self._offsets[n] = buf, offs
+
+    @classmethod
+    def _aligned(cls, n: int) -> int:
+        return (n + cls.COMPACT_ALIGN - 1) // cls.COMPACT_ALIGN * cls.COMPACT_ALIGN
+
+    @classmethod
+    def from_model_path(cls, cfg: ModelConfig, model_path: str, pinned: bool = True,
+                        names: Optional[Sequence[str]] = None) -> "CompactHostStore":
+        from .stream import FileLayerSource
+        return cls(FileLayerSource(cfg, model_path, names=names), pinned)
+
+    @property
+    def total_bytes(self) -> int:
+        return sum(b.numel() for b in self.buffers.values())
+
+    def pinned_bytes(self) -> int:
+        return self.total_bytes
+
+    def plan(self, name: str):
+        return self.files.plan(name)
+
+    def fold_norms(self, device):
+        raise ValueError("--weight_cache host keeps an FP8 checkpoint's bytes as they are in the files: norms "
+                         "cannot be folded into FP8 weights (they are folded as each layer lands)")
+
+    def read_into(self, name: str, dst: torch.Tensor) -> None:
+        self.files.read_into(name, dst)
+
+    def prepare_device(self, device):
+        return self.files.prepare_device(device)
+
+    def stream_into(self, name: str, dst: torch.Tensor, stream, lo: int = 0, hi: Optional[int] = None,
+                    cast: bool = True) -> int:
+        """Enqueue image bytes [lo, hi) of ``name`` into the HBM byte tensor ``dst`` (whose byte 0 is
+        image byte ``lo``) on ``stream``: one async H2D per tensor, then (``cast``) the in-place
+        expansions.  Returns the host bytes copied."""
+        pl = self.files.plan(name)
+        hi = pl.nbytes if hi is None else hi
+        pl.pieces(lo, hi)                   # (refuses a range through an FP8 tensor)
+        buf, offs, total = self.buffers[name], self._offsets[name], 0
+        with torch.cuda.stream(stream):
+            for r in pl.runs:
+                a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
+                if a >= b:
+                    continue
+                if r.is_fp8:
+                    src, d0 = buf[offs[r.hf_name]:offs[r.hf_name] + r.numel], r.land_off - lo
+                else:
+                    s0 = offs[r.hf_name] + (a - r.img_off)
+                    src, d0 = buf[s0:s0 + (b - a)], a - lo
+                dst[d0:d0 + src.numel()].copy_(src, non_blocking=True)
+                total += src.numel()
+            if cast:
+                self.cast_on_gpu(name, dst, lo, hi)
+        self.h2d_bytes += total
+        return total
+
+    def cast_on_gpu(self, name: str, dst: torch.Tensor, lo: int = 0, hi: Optional[int] = None) -> None:
+        self.files.cast_on_gpu(name, dst, lo, hi)
+
+    def stats(self) -> Dict[str, float]:
+        return {"h2d_bytes": float(self.h2d_bytes), "pinned_bytes": float(self.total_bytes)}
+
+    def close(self) -> None:
+        self.files.close()
 
 
 def shard_chunk_bytes(nbytes: int, world: int, align: int = 4096) -> int:

@@ -98,8 +98,16 @@ def _load_shard(path: str) -> Dict[str, torch.Tensor]:
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True) -> List[str]:
-    """Convert an HF checkpoint directory into per-layer safetensors files."""
+def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize: str = None,
+                      fp8_scale: str = "channel") -> List[str]:
+    """Convert an HF checkpoint directory into per-layer safetensors files.
+
+    An FP8 (e4m3fn) source checkpoint passes through unchanged: its scale tensors (``weight_scale``,
+    ``weight_scale_inv``, ``input_scale``) follow their weight into the layer file.
+    ``quantize="fp8"`` writes the decoder layers' projection weights as FP8 with ``fp8_scale``
+    scales (fp8.quantize_state_dict)."""
+    if quantize not in (None, "fp8"):
+        raise ValueError(f"--quantize {quantize!r}: only fp8 is supported")
     os.makedirs(out_dir, exist_ok=True)
     for fn in glob.glob(os.path.join(src_dir, "*")):
         base = os.path.basename(fn)
@@ -145,7 +153,11 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True) -> List[
         for p in layer_params[l]:
             sd[canonical_param(p)] = cache[wmap[p]][p]
         assert len(sd) == len(layer_params[l]), f"Should have {len(layer_params[l])} keys for {l}"
-        save_file(normalize_expert_names(model_type, sd), layer_file(out_dir, l))
+        out_sd = normalize_expert_names(model_type, sd)
+        if quantize:
+            from ..fp8 import quantize_state_dict
+            out_sd = quantize_state_dict(out_sd, fp8_scale)
+        save_file(out_sd, layer_file(out_dir, l))
         written.append(l)
         if tied and l == "model.embed_tokens":
             # tie_word_embeddings checkpoints store no lm_head: give the head its own layer file so

@@ -24,9 +24,19 @@ import torch
 DTYPES = {
     "F16": torch.float16, "BF16": torch.bfloat16, "F32": torch.float32, "F64": torch.float64,
     "I8": torch.int8, "U8": torch.uint8, "I16": torch.int16, "I32": torch.int32, "I64": torch.int64,
-    "BOOL": torch.bool,
+    "BOOL": torch.bool, "F8_E4M3": torch.float8_e4m3fn,      # (weight-only FP8 checkpoints: fp8.py)
 }
 DTYPE_NAMES = {v: k for k, v in DTYPES.items()}
+# FP8 formats the loader refuses by name (fp8.py): OCP e5m2 and the fnuz encodings
+REFUSED_FP8 = ("F8_E5M2", "F8_E4M3FNUZ", "F8_E5M2FNUZ")
+
+
+def dtype_of(name: str, tensor: str = "", path: str = "") -> torch.dtype:
+    """torch dtype of a safetensors dtype string; TypeError naming the tensor for the FP8 formats
+    other than e4m3fn, KeyError for an unknown string."""
+    if name in REFUSED_FP8:
+        raise TypeError(f"{path}: {tensor} has dtype {name}; of the FP8 formats only F8_E4M3 (OCP e4m3fn) is supported")
+    return DTYPES[name]
 
 
 @dataclass(frozen=True)
@@ -56,7 +66,7 @@ def read_header(path: str) -> Tuple[Dict[str, TensorInfo], dict]:
     infos = {}
     for name, e in hdr.items():
         b, en = e["data_offsets"]
-        infos[name] = TensorInfo(name, DTYPES[e["dtype"]], tuple(e["shape"]), base + b, base + en)
+        infos[name] = TensorInfo(name, dtype_of(e["dtype"], name, path), tuple(e["shape"]), base + b, base + en)
     return infos, meta
 
 

@@ -4,6 +4,8 @@
     python prepare_weights.py <hf_dir> <new_file_dir>
     python prepare_weights.py --synthetic llama2-7b <new_file_dir> [--seed 0] [--dtype bfloat16]
                               [--unique_layers K]   (decoder layers >= K hard-link to layer i % K)
+    either form: --quantize fp8 [--fp8_scale channel|tensor|block128]
+                 (decoder projection weights as FP8 e4m3 + fp32 scales: half the weight bytes)
 """
 import argparse
 import sys
@@ -25,6 +27,13 @@ def main(argv=None):
                     help="--synthetic: checkpoint dtype")
     ap.add_argument("--unique_layers", type=int, default=0,
                     help="--synthetic: write K distinct decoder layers, hard-link the rest (disk-limited boxes)")
+    ap.add_argument("--quantize", choices=["fp8"], default=None,
+                    help="write the decoder layers' 2-D projection weights (q/k/v/o, gate/up/down, fused and "
+                         "expert weights) as FP8 e4m3 with fp32 scales; router, norms, biases, embedding and "
+                         "head stay as they are")
+    ap.add_argument("--fp8_scale", choices=["channel", "tensor", "block128"], default="channel",
+                    help="--quantize fp8: one scale per output channel / per tensor (weight_scale) or per "
+                         "128x128 block (weight_scale_inv)")
     a = ap.parse_args(argv)
     if a.synthetic:
         import torch
@@ -32,9 +41,10 @@ def main(argv=None):
         from flexible_llm_sharding_amd.utils.synthetic import write_synthetic_checkpoint
         kw = {} if a.num_hidden_layers is None else {"num_hidden_layers": a.num_hidden_layers}
         write_synthetic_checkpoint(preset(a.bin_dir, **kw), a.new_file_dir, seed=a.seed, std=a.std,
-                                   dtype=getattr(torch, a.dtype), unique_layers=a.unique_layers)
+                                   dtype=getattr(torch, a.dtype), unique_layers=a.unique_layers,
+                                   quantize=a.quantize, fp8_scale=a.fp8_scale)
     else:
-        split_into_layers(a.bin_dir, a.new_file_dir)
+        split_into_layers(a.bin_dir, a.new_file_dir, quantize=a.quantize, fp8_scale=a.fp8_scale)
     return 0
 
 

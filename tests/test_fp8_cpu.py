@@ -1,0 +1,472 @@
+"""Weight-only FP8 (e4m3fn) checkpoints without a GPU: the host definition (fp8.py), the
+converter, the byte plan of an FP8 layer, the torch-backend engine and ``main.py`` against the fp16
+twin (bit for bit), HF-style sources in both scale conventions, the refusals and the host-cache
+sizing."""
+import json
+import os
+import pickle
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fp8_ref as fr  # noqa: E402
+
+from flexible_llm_sharding_amd import fp8  # noqa: E402
+from flexible_llm_sharding_amd.config import preset  # noqa: E402
+from flexible_llm_sharding_amd.engine import ShardedRunner  # noqa: E402
+from flexible_llm_sharding_amd.models.layout import (layer_kind, layer_layout, pack_layer,  # noqa: E402
+                                                     placements)
+from flexible_llm_sharding_amd.runtime.stream import KIND_RAW, FileLayerSource, LayerPlan  # noqa: E402
+from flexible_llm_sharding_amd.runtime.weights import CompactHostStore, HostStore, layer_pieces  # noqa: E402
+from flexible_llm_sharding_amd.utils.layer_format import layer_file, split_into_layers  # noqa: E402
+from flexible_llm_sharding_amd.utils.safetensors_io import (load_file, read_header,  # noqa: E402
+                                                            save_file)
+from flexible_llm_sharding_amd.utils.synthetic import (synthetic_layer_state_dict,  # noqa: E402
+                                                       write_synthetic_checkpoint)
+from flexible_llm_sharding_amd.utils.tokenizer import load_tokenizer  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ALL = torch.arange(256, dtype=torch.int16).to(torch.uint8)
+
+
+# ------------------------------------------------------------------ definition
+def test_table_is_e4m3fn():
+    t = fp8.table()
+    assert t.dtype == torch.float32 and t.shape == (256,)
+    assert torch.isnan(t[0x7F]) and torch.isnan(t[0xFF]) and int(torch.isnan(t).sum()) == 2
+    assert t[0x7E] == 448.0 and t[0xFE] == -448.0 and t[0x01] == 2.0 ** -9 and t[0x38] == 1.0
+    # every value is exact in fp16
+    ok = ~torch.isnan(t)
+    assert torch.equal(t[ok].half().float(), t[ok])
+
+
+@pytest.mark.parametrize("scale", fr.EXTREME_SCALES)
+def test_dequantize_all_patterns(scale):
+    """All 256 patterns x the scales that reach the fp16-subnormal and the overflow end."""
+    bits = ALL.reshape(16, 16)
+    s = torch.tensor([scale], dtype=torch.float32)
+    got = fp8.dequantize(bits, s)
+    want = fr.torch_dequant(bits, s.reshape(1, 1))
+    assert got.dtype == torch.float16 and fr.same_bits(got, want)
+    if scale == 2.0 ** 12:
+        assert torch.isinf(got[~torch.isnan(got)]).any()          # overflow goes to +-inf
+    if scale == 2.0 ** -20:
+        tiny = got[~torch.isnan(got)].float().abs()
+        assert ((tiny > 0) & (tiny < 2.0 ** -14)).any()          # fp16 subnormals are produced
+
+
+def test_dequantize_scale_kinds_ragged_blocks():
+    g = torch.Generator().manual_seed(0)
+    out, inn = 200, 328                                          # 2 x 3 ragged 128-blocks
+    bits = torch.randint(0, 256, (out, inn), generator=g, dtype=torch.int16).to(torch.uint8)
+    for shape in ((), (1,)):
+        s = (torch.rand(shape, generator=g) + 0.5) * 1e-2
+        assert fr.same_bits(fp8.dequantize(bits, s), fr.torch_dequant(bits, s.reshape(1, 1)))
+    for shape in ((out,), (out, 1)):
+        s = (torch.rand(shape, generator=g) + 0.5) * 1e-2
+        assert fr.same_bits(fp8.dequantize(bits, s), fr.torch_dequant(bits, s.reshape(out, 1)))
+    s = (torch.rand(2, 3, generator=g) + 0.5) * 1e-2
+    full = torch.empty(out, inn)
+    for r in range(out):
+        for c in range(0, inn, 8):
+            full[r, c:c + 8] = s[r // 128, c // 128]
+    assert fr.same_bits(fp8.dequantize(bits, s), fr.torch_dequant(bits, full))
+    # bf16 / fp16 scales are widened exactly; float8 input is the same as its bytes
+    sb = s.to(torch.bfloat16)
+    assert fr.same_bits(fp8.dequantize(bits.view(torch.float8_e4m3fn), sb), fr.torch_dequant(bits, _blocks(sb.float(), out, inn)))
+    with pytest.raises(ValueError):
+        fp8.dequantize(bits, torch.ones(3, 2))
+
+
+def _blocks(s, out, inn):
+    return s.repeat_interleave(128, 0)[:out].repeat_interleave(128, 1)[:, :inn]
+
+
+# ------------------------------------------------------------------- converter
+@pytest.mark.parametrize("kind", ["channel", "tensor", "block128"])
+def test_quantize_error_bound(kind):
+    """|dequantize(quantize(w)) - w| <= 2^-4 |w| + 2^-10 s + 2^-11 |w|: e4m3's 3 mantissa bits, its
+    subnormal step (2^-9 s, rounded: half of it), and the fp16 rounding."""
+    g = torch.Generator().manual_seed(1)
+    w = (torch.randn(200, 328, generator=g) * 0.05).half()
+    w[7] = 0                                                     # an all-zero row
+    w[130:140, 200:210] *= 50
+    bits, scale = fp8.quantize(w, kind)
+    assert bits.dtype == torch.float8_e4m3fn and scale.dtype == torch.float32
+    assert tuple(scale.shape) == {"channel": (200, 1), "tensor": (1,), "block128": (2, 3)}[kind]
+    s = fp8.expand_scale(scale, (200, 328)).expand(200, 328)
+    amax = {"channel": w.float().abs().amax(1, keepdim=True).expand(200, 328),
+            "tensor": w.float().abs().amax().expand(200, 328),
+            "block128": None}[kind]
+    if amax is not None:
+        assert torch.equal(s, torch.where(amax > 0, amax / 448.0, torch.ones_like(amax)))
+    if kind == "channel":
+        assert scale[7, 0] == 1.0
+    d = fp8.dequantize(bits, scale).float()
+    wf = w.float()
+    assert not torch.isnan(d).any()
+    assert torch.equal(d[7], torch.zeros(328))
+    bound = 2.0 ** -4 * wf.abs() + 2.0 ** -10 * s + 2.0 ** -11 * wf.abs()
+    assert bool(((d - wf).abs() <= bound).all()), float(((d - wf).abs() - bound).max())
+
+
+@pytest.mark.parametrize("name", ["tiny-qwen2", "tiny-phi3", "tiny-qwen2-moe", "tiny-mixtral"])
+def test_quantize_state_dict_touches_projections_only(name):
+    cfg = preset(name)
+    sd = synthetic_layer_state_dict(cfg, "model.layers.0", seed=2, std=0.05)
+    q = fp8.quantize_state_dict(sd, "channel")
+    n_q = 0
+    for k, v in sd.items():
+        proj = v.dim() == 2 and ("_proj.weight" in k or ".experts." in k) and "shared_expert_gate" not in k
+        if proj:
+            assert q[k].dtype == torch.float8_e4m3fn and q[k + "_scale"].dtype == torch.float32, k
+            n_q += 1
+        else:                                                    # router, norms, biases, shared-expert gate
+            assert q[k].dtype == v.dtype and torch.equal(q[k].view(torch.int16), v.view(torch.int16)), k
+            assert k + "_scale" not in q
+    assert n_q and len(q) == len(sd) + n_q
+    assert fp8.quantize_state_dict(sd, "block128")[next(k for k in q if k.endswith("_scale"))[:-6] + "_scale_inv"].dim() == 2
+    for lay in ("model.embed_tokens", "model.norm", "lm_head"):
+        other = synthetic_layer_state_dict(cfg, lay, seed=2)
+        assert all(v.dtype == torch.float16 for v in fp8.quantize_state_dict(other, "channel").values())
+    again = fp8.quantize_state_dict(q, "channel")                # an FP8 state dict passes through
+    assert set(again) == set(q) and all(again[k] is q[k] for k in q)
+
+
+def test_safetensors_f8_round_trip(tmp_path):
+    bits = ALL.reshape(16, 16).view(torch.float8_e4m3fn)
+    p = str(tmp_path / "t.safetensors")
+    save_file({"a.weight": bits, "a.weight_scale": torch.ones(16, 1)}, p)
+    infos, _ = read_header(p)
+    assert infos["a.weight"].dtype == torch.float8_e4m3fn and infos["a.weight"].nbytes == 256
+    with open(p, "rb") as f:
+        assert b'"F8_E4M3"' in f.read(512)
+    back = load_file(p)["a.weight"]
+    assert back.dtype == torch.float8_e4m3fn and torch.equal(back.view(torch.uint8), ALL.reshape(16, 16))
+    from flexible_llm_sharding_amd.runtime import hostmem
+    native = hostmem.read_header_native(p)
+    if native is not None:
+        assert native["a.weight"].dtype == torch.float8_e4m3fn
+        assert torch.equal(hostmem.read_safetensors(p)["a.weight"].view(torch.uint8), ALL.reshape(16, 16))
+
+
+# ------------------------------------------------------------------------ plan
+@pytest.fixture(scope="module")
+def pairs(tmp_path_factory):
+    root = tmp_path_factory.mktemp("fp8_pairs")
+    cache = {}
+
+    def get(name, scale, scale_dtype=None):
+        key = (name, scale, scale_dtype)
+        if key not in cache:
+            cache[key] = fr.make_pair(os.path.join(str(root), str(len(cache))), name, scale, scale_dtype=scale_dtype)
+        return cache[key]
+    return get
+
+
+@pytest.mark.parametrize("name,scale", [("tiny", "channel"), ("tiny-phi3", "block128"), ("tiny-mixtral", "channel")])
+def test_layer_plan_of_fp8_layer(pairs, name, scale):
+    cfg, q, twin = pairs(name, scale)
+    lname = "model.layers.1"
+    plan = LayerPlan(cfg, lname, layer_file(q, lname))
+    sd = load_file(layer_file(q, lname))
+    lay = layer_layout(cfg, "decoder")
+    pls = {p.hf_name: p for p in placements(cfg, lname)}
+    assert plan.nbytes == lay.nbytes
+    # file_bytes counts the real bytes: 1 per FP8 weight, 2 per fp16 one, no scale tensors
+    assert plan.file_bytes == fr.file_tensor_bytes(q, lname)
+    assert plan.fp8_tensors == sum(1 for v in sd.values() if v.dtype == torch.float8_e4m3fn) > 0
+    assert plan.file_bytes < 0.6 * sum(2 * p.numel for p in pls.values())
+    infos, _ = read_header(layer_file(q, lname))
+    pieces = plan.pieces()
+    assert len(pieces) == len(pls) and [p[0] for p in pieces] == sorted(p[0] for p in pieces)
+    by_off = {infos[k].begin: k for k in pls}
+    for fo, nb, do, kind in pieces:
+        k = by_off[fo]
+        assert kind == KIND_RAW
+        if sd[k].dtype == torch.float8_e4m3fn:
+            # raw bytes at the landing position: the upper half of the tensor's own 2 * numel region
+            assert nb == pls[k].numel and do == pls[k].offset + pls[k].numel
+        else:
+            assert nb == 2 * pls[k].numel and do == pls[k].offset
+    # the attention / MLP pieces hold whole tensors and are accepted; offsets are relative to lo
+    (a0, a1), (m0, m1) = layer_pieces(lay)
+    pa, pm = plan.pieces(a0, a1), plan.pieces(m0, m1)
+    assert sorted(pa + [(f, n, d + m0, k) for f, n, d, k in pm]) == sorted(pieces)
+    assert len(plan.fp8_runs(a0, a1)) + len(plan.fp8_runs(m0, m1)) == plan.fp8_tensors
+    # a range through an FP8 tensor is refused
+    r = next(r for r in plan.runs if r.is_fp8)
+    for lo, hi in ((r.img_off + 2, r.img_off + 2 * r.numel), (0, r.img_off + r.numel), (r.img_off, r.img_off + 2 * r.numel - 2)):
+        with pytest.raises(ValueError, match="FP8"):
+            plan.pieces(lo, hi)
+    # the host image equals pack_layer of the twin's tensors byte for byte
+    src = FileLayerSource(cfg, q)
+    for n in cfg.layer_names():
+        got = torch.zeros(src.nbytes(n), dtype=torch.uint8)
+        src.read_into(n, got)
+        want = pack_layer(cfg, n, load_file(layer_file(twin, n)))
+        assert torch.equal(got, want), n
+        assert torch.equal(pack_layer(cfg, n, load_file(layer_file(q, n))), want), n
+    part = torch.zeros(m1 - m0, dtype=torch.uint8)
+    src.read_range_into(lname, part, m0, m1)
+    assert torch.equal(part, pack_layer(cfg, lname, load_file(layer_file(twin, lname)))[m0:m1])
+    assert src.fp8_tensors() == plan.fp8_tensors * cfg.num_hidden_layers
+    assert src.file_bytes() == sum(fr.file_tensor_bytes(q, n) for n in cfg.layer_names())
+
+
+# ---------------------------------------------------------------------- engine
+def _scores(cfg, src, path, prompts, **kw):
+    r = ShardedRunner(cfg, src, "cpu", load_tokenizer(path), **kw)
+    out = r(prompts)
+    r.close()
+    return out
+
+
+@pytest.mark.parametrize("name,scale,scale_dtype", [
+    ("tiny", "channel", None), ("tiny-qwen2", "tensor", None), ("tiny-phi3", "block128", None),
+    ("tiny", "channel", torch.bfloat16), ("tiny-mixtral", "block128", torch.float16)])
+def test_engine_fp8_bitwise_equals_twin_cpu(pairs, name, scale, scale_dtype):
+    cfg, q, twin = pairs(name, scale, scale_dtype)
+    prompts = fr.prompts_for(cfg)
+    want = _scores(cfg, FileLayerSource(cfg, twin), twin, prompts)
+    got = _scores(cfg, FileLayerSource(cfg, q), q, prompts, layer_num_per_shard=2)
+    compact = _scores(cfg, CompactHostStore(FileLayerSource(cfg, q), pinned=False), q, prompts)
+    host = _scores(cfg, HostStore.from_model_path(cfg, q, pinned=False), q, prompts)
+    for w, a, b, c in zip(want, got, compact, host):
+        assert w.dtype == np.float16
+        assert np.array_equal(w.view(np.uint16), a.view(np.uint16))
+        assert np.array_equal(w.view(np.uint16), b.view(np.uint16))
+        assert np.array_equal(w.view(np.uint16), c.view(np.uint16))
+    # (the quantisation is not a no-op: the fp16 original scores differently)
+    if scale_dtype is None and name == "tiny":
+        orig = os.path.join(os.path.dirname(q), "orig")
+        write_synthetic_checkpoint(cfg, orig, seed=3, std=0.05)
+        o = _scores(cfg, FileLayerSource(cfg, orig), orig, prompts)
+        assert any(not np.array_equal(x, y) for x, y in zip(o, want))
+
+
+def _main(args, cwd):
+    env = dict(os.environ, PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py")] + args, cwd=cwd, env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r
+
+
+def test_main_fp8_equals_twin(tmp_path):
+    """prepare_weights.py --synthetic --quantize fp8, then main.py on it and on its twin: the same
+    output pickle; --metrics_json reports the file bytes and the FP8 tensor count."""
+    q, twin = str(tmp_path / "q"), str(tmp_path / "twin")
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "prepare_weights.py"), "tiny", q, "--synthetic",
+                        "--quantize", "fp8", "--fp8_scale", "block128", "--std", "0.05"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert any(v.dtype == torch.float8_e4m3fn for v in load_file(layer_file(q, "model.layers.0")).values())
+    fp8.write_twin(q, twin)
+    cfg = preset("tiny")
+    pp = tmp_path / "prompts.pkl"
+    pickle.dump(fr.prompts_for(cfg), open(pp, "wb"))
+    outs = {}
+    for tag, path, extra in (("q_host", q, ["--weight_cache", "host"]), ("q_stream", q, ["--weight_cache", "stream"]),
+                             ("twin", twin, [])):
+        out = tmp_path / f"{tag}.pkl"
+        _main(["--model_path", path, "--prompt_pickle", str(pp), "--output_file", str(out), "--num_gen_token", "2",
+               "--metrics_json", str(tmp_path / f"{tag}.json")] + extra, str(tmp_path))
+        outs[tag] = open(out, "rb").read()
+    assert outs["q_host"] == outs["twin"] and outs["q_stream"] == outs["twin"]
+    m = json.load(open(tmp_path / "q_host.json"))
+    src = FileLayerSource(cfg, q)
+    assert m["fp8_tensors"] == src.fp8_tensors() == 14 and m["weight_file_bytes"] == src.file_bytes()
+    assert m["weight_pinned_bytes"] >= m["weight_file_bytes"]
+    mt = json.load(open(tmp_path / "twin.json"))
+    assert mt["fp8_tensors"] == 0 and mt["weight_file_bytes"] > m["weight_file_bytes"]
+
+
+# ------------------------------------------------------------- HF-style source
+@pytest.mark.parametrize("convention", ["compressed-tensors", "block"])
+def test_hf_style_fp8_source(tmp_path, convention):
+    """A hand-built HF directory in each scale convention (with input_scale tensors and a
+    quantization_config): split_into_layers passes it through, and it runs like its twin."""
+    cfg = preset("tiny")
+    hf, out, twin = str(tmp_path / "hf"), str(tmp_path / "layers"), str(tmp_path / "twin")
+    write_synthetic_checkpoint(cfg, hf, seed=4, std=0.05)          # config + tokenizer (+ layer files, removed)
+    sd = {}
+    for n in cfg.layer_names():
+        sd.update(load_file(layer_file(hf, n)))
+        os.remove(layer_file(hf, n))
+    full = {}
+    for k, v in sd.items():
+        if fp8.is_quantized_name(k):
+            kind = "block128" if convention == "block" else ("tensor" if "o_proj" in k else "channel")
+            bits, s = fp8.quantize(v, kind)
+            full[k] = bits
+            if convention == "block":
+                full[k + "_scale_inv"] = s
+            else:
+                full[k + "_scale"] = s.reshape(-1) if "k_proj" in k else (s.reshape(()) if kind == "tensor" else s)
+                full[k[:-len(".weight")] + ".input_scale"] = torch.tensor(0.02)
+        else:
+            full[k] = v
+    save_file(full, os.path.join(hf, "model.safetensors"))
+    c = json.load(open(os.path.join(hf, "config.json")))
+    c["quantization_config"] = {"quant_method": "fp8", "weight_block_size": [128, 128]}
+    json.dump(c, open(os.path.join(hf, "config.json"), "w"))
+    split_into_layers(hf, out, verbose=False)
+    assert json.load(open(os.path.join(out, "config.json")))["quantization_config"]["quant_method"] == "fp8"
+    lf = load_file(layer_file(out, "model.layers.0"))
+    qk = "model.layers.0.self_attn.q_proj.weight"
+    assert torch.equal(lf[qk].view(torch.uint8), full[qk].view(torch.uint8))     # unchanged bytes
+    if convention == "block":
+        assert qk + "_scale_inv" in lf
+    else:
+        assert qk + "_scale" in lf and "model.layers.0.self_attn.q_proj.input_scale" in lf
+    fp8.write_twin(out, twin)
+    assert not any(fp8.is_scale_name(k) for k in load_file(layer_file(twin, "model.layers.0")))
+    from flexible_llm_sharding_amd.config import ModelConfig
+    cfg2 = ModelConfig.from_pretrained(out)                                      # quantization_config is ignored
+    prompts = fr.prompts_for(cfg2)
+    src = FileLayerSource(cfg2, out)
+    assert len(src.ignored_scales()) == (0 if convention == "block" else 14)
+    want = _scores(cfg2, FileLayerSource(cfg2, twin), twin, prompts)
+    got = _scores(cfg2, src, out, prompts)
+    assert all(np.array_equal(a, b) for a, b in zip(want, got))
+
+
+# -------------------------------------------------------------------- refusals
+def _layer_with(tmp_path, cfg, edit):
+    d = str(tmp_path / "m")
+    write_synthetic_checkpoint(cfg, d, seed=1, std=0.05, quantize="fp8")
+    p = layer_file(d, "model.layers.0")
+    sd = load_file(p)
+    edit(sd)
+    save_file(sd, p)
+    return d, p
+
+
+Q = "model.layers.0.self_attn.q_proj.weight"
+
+
+@pytest.mark.parametrize("case", ["no_scale", "both", "shape", "inv_channel", "scale_dtype"])
+def test_refused_fp8_tensors(tmp_path, case):
+    cfg = preset("tiny")
+
+    def edit(sd):
+        if case == "no_scale":
+            del sd[Q + "_scale"]
+        elif case == "both":
+            sd[Q + "_scale_inv"] = torch.ones(2, 2)
+        elif case == "shape":
+            sd[Q + "_scale"] = torch.ones(3)
+        elif case == "inv_channel":
+            sd[Q + "_scale_inv"] = sd.pop(Q + "_scale")
+        else:
+            sd[Q + "_scale"] = torch.ones(256, 1, dtype=torch.int32)
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(TypeError, match="q_proj.weight.*(F8_E4M3|dtype)"):
+        LayerPlan(cfg, "model.layers.0", p)
+    if case != "scale_dtype":
+        with pytest.raises(TypeError, match="F8_E4M3"):
+            pack_layer(cfg, "model.layers.0", load_file(p))
+
+
+@pytest.mark.parametrize("dtype", ["F8_E5M2", "F8_E4M3FNUZ", "F8_E5M2FNUZ"])
+def test_refused_fp8_formats(tmp_path, dtype):
+    cfg = preset("tiny")
+    d, p = _layer_with(tmp_path, cfg, lambda sd: None)
+    raw = open(p, "rb").read()
+    n = int.from_bytes(raw[:8], "little")
+    hdr = json.loads(raw[8:8 + n])
+    hdr[Q]["dtype"] = dtype
+    hb = json.dumps(hdr, separators=(",", ":")).encode()
+    hb += b" " * ((8 - len(hb) % 8) % 8)
+    open(p, "wb").write(len(hb).to_bytes(8, "little") + hb + raw[8 + n:])
+    with pytest.raises(TypeError, match=f"q_proj.weight.*{dtype}"):
+        LayerPlan(cfg, "model.layers.0", p)
+    with pytest.raises(TypeError, match=dtype):
+        read_header(p)
+
+
+def test_int8_still_rejected(tmp_path):
+    cfg = preset("tiny")
+    sd = synthetic_layer_state_dict(cfg, "model.layers.0")
+    sd[Q] = sd[Q].to(torch.int8)
+    with pytest.raises(AssertionError, match="int8"):
+        pack_layer(cfg, "model.layers.0", sd)
+
+
+def test_unlisted_family_accepts_scale_tensors(pairs):
+    """A config of an unlisted Llama-like family refuses extra tensors, but not an FP8 weight's scales."""
+    import dataclasses
+    cfg, q, twin = pairs("tiny", "channel")
+    other = dataclasses.replace(cfg, model_type="some_llama_like") if dataclasses.is_dataclass(cfg) else None
+    if other is None:
+        other = preset("tiny")
+        other.model_type = "some_llama_like"
+    plan = LayerPlan(other, "model.layers.0", layer_file(q, "model.layers.0"))
+    assert plan.fp8_tensors == 7
+    sd = load_file(layer_file(q, "model.layers.0"))
+    sd["model.layers.0.self_attn.q_norm.weight_scale"] = torch.ones(1)          # (no such weight)
+    with pytest.raises(NotImplementedError):
+        pack_layer(other, "model.layers.0", sd)
+
+
+def test_refused_dp_weight_shard_and_fold(pairs):
+    from flexible_llm_sharding_amd.api import check_fp8_dp_shard
+    cfg, q, twin = pairs("tiny", "channel")
+    args = types.SimpleNamespace(model_path=q, synthetic=None, score_mode="next_token")
+    with pytest.raises(ValueError, match="--dp_weight_shard"):
+        check_fp8_dp_shard(args, cfg)
+    check_fp8_dp_shard(types.SimpleNamespace(model_path=twin, synthetic=None, score_mode="next_token"), cfg)
+    check_fp8_dp_shard(types.SimpleNamespace(model_path=None, synthetic="tiny", score_mode="next_token"), cfg)
+    store = CompactHostStore(FileLayerSource(cfg, q), pinned=False)
+    assert store.norms_folded is False and store.host_buffer("model.layers.0") is None
+    with pytest.raises(ValueError, match="--weight_cache host"):
+        store.fold_norms("cpu")
+
+
+def test_dp_weight_shard_refused_by_build_runner(pairs, tmp_path):
+    """--data_parallel with --dp_weight_shard true on two ranks refuses an FP8 checkpoint before
+    anything is loaded; the flag's name is in the message."""
+    from flexible_llm_sharding_amd.api import build_runner
+    from flexible_llm_sharding_amd.utils.cli import parse_args
+    cfg, q, twin = pairs("tiny", "channel")
+    args = parse_args(["--model_path", q, "--prompt_pickle", "p.pkl", "--output_file", "o.pkl", "--data_parallel",
+                       "--dp_weight_shard", "true"])
+    comm = types.SimpleNamespace(world=2, rank=0, active=True)
+    with pytest.raises(ValueError, match="--dp_weight_shard"):
+        build_runner(args, cfg, "cpu", comm, load_tokenizer(q))
+
+
+# ---------------------------------------------------------------------- sizing
+def test_resolve_weight_cache_sizes_fp8_by_file_bytes(pairs):
+    from flexible_llm_sharding_amd.api import build_source, resolve_weight_cache
+    from flexible_llm_sharding_amd.parallel.comm import Comm
+    cfg, q, twin = pairs("tiny", "channel")
+    names = cfg.layer_names()
+    comm = Comm(0, 1)
+    src, tsrc = FileLayerSource(cfg, q), FileLayerSource(cfg, twin)
+    image = sum(layer_layout(cfg, layer_kind(n)).nbytes for n in names)
+    files = src.file_bytes()
+    assert files < image and tsrc.file_bytes() <= image
+    between = (files + image) / 2 / 1e9                          # fits the FP8 files, not the fp16 image
+
+    def args(mode, gb, path=q):
+        return types.SimpleNamespace(weight_cache=mode, host_mem_gb=gb, synthetic=None, model_path=path,
+                                     layer_num_per_shard=1, data_parallel=False, verbose=False)
+    assert resolve_weight_cache(args("auto", between), cfg, comm, names, sliced=False, source=src) == "host"
+    assert resolve_weight_cache(args("auto", between), cfg, comm, names, sliced=False, source=tsrc) == "stream"
+    assert resolve_weight_cache(args("auto", between), cfg, comm, names, sliced=False) == "stream"
+    with pytest.raises(SystemExit):
+        resolve_weight_cache(args("host", files / 2 / 1e9), cfg, comm, names, sliced=False, source=src)
+    # build_source: an FP8 checkpoint resolves host to the compact store, a pure fp16 one to today's
+    st = build_source(args("host", between), cfg, comm, torch.device("cpu"))
+    assert isinstance(st, CompactHostStore) and st.total_bytes < 0.75 * image
+    assert sum(st._aligned(r.numel * min(r.src_es, 2)) for n in names for r in st.plan(n).runs) == st.total_bytes
+    assert isinstance(build_source(args("stream", between), cfg, comm, torch.device("cpu")), FileLayerSource)
+    assert type(build_source(args("host", 1.0, twin), cfg, comm, torch.device("cpu"))) is HostStore
