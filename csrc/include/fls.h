@@ -208,6 +208,20 @@ int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stre
 int fls_dequant_fp8(void* region, uint64_t n, const float* scale, int kind, uint64_t cols, fls_stream_t s);
 int fls_dequant_fp8_launches(uint64_t n);
 int fls_dequant_fp8_tail(void);
+// weight-only INT4 (W4A16, symmetric, group scales) expansion in place (csrc/kernels/dequant.hip;
+// flexible_llm_sharding_amd/int4.py holds the definition and the landing layout, region_layout()).
+// region: the tensor's 2n-byte image region (2-byte aligned) in which the n / 2 bytes of nibbles and
+// the n / group raw scales (scale_dtype 0 fp16, 1 bf16, 2 fp32) have landed segment by segment;
+// afterwards it holds n fp16 values, w16[i] = fp16_rne(fp32(nibble(i) - 8) * fp32(scale[i / group])).
+// Uses no other device memory: fls_dequant_int4_launches(n, group, scale_es) stream-ordered launches
+// on s, the last a single block of at most fls_dequant_int4_tail() weights.  hipErrorInvalidValue,
+// with nothing launched, for a missing pointer, an odd region address, group % 32 != 0,
+// n % group != 0 or an unknown scale dtype; n == 0 returns 0.
+int fls_dequant_int4(void* region, uint64_t n, uint64_t group, int scale_dtype, fls_stream_t s);
+int fls_dequant_int4_launches(uint64_t n, uint64_t group, int scale_es);
+int fls_dequant_int4_tail(void);
+// launch j of that chain: out[6] = {a, b, packed offset, scale offset, first group, groups} (host only)
+int fls_dequant_int4_segment(uint64_t n, uint64_t group, int scale_es, int j, uint64_t* out);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0
 int fls_gemv_skinny(const void* x, const void* w, void* c, int M, int N, int K, int ldx, int ldw, int ldc,
                     fls_stream_t s);

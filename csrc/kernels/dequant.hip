@@ -172,3 +172,197 @@ extern "C" int fls_dequant_fp8(void* region, uint64_t n, const float* scale, int
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Weight-only INT4 (W4A16, symmetric, group scales) expansion in place (flexible_llm_sharding_amd/int4.py
+// holds the definition and, in region_layout(), the landing layout this file mirrors).
+//
+//   w16[i] = fp16_rne( fp32(nibble(i) - 8) * fp32(scale[i / g]) )
+//
+// The inputs of a tensor of N weights land in its own 2N-byte region segment by segment, one segment
+// per launch, stacked downwards from the top of the region in reverse launch order:
+//
+//   [ ... free ... | scales_0 | packed_0 | scales_1 | packed_1 | ... | scales_tail | packed_tail ]
+//
+// Launch j expands elements [a_j, b_j) and writes bytes [2 a_j, 2 b_j); 2 b_j <= offset(scales_j), so
+// it touches nothing unread.  scales_j holds the groups that END in [a_j, b_j); the group that
+// straddles b_j is read from the next segment that holds scales, which lies above.  The tail (at
+// most kTail4 weights) is one block that reads its nibbles and scales into registers, barriers, and
+// writes.  Segments are sized from the top, each as large as the rule allows: the part that is left
+// shrinks by 1 / (1/4 + es / 2g) per launch (10 launches for 8192 x 28672 at g = 32 with fp32 scales).
+//
+// Each thread expands 32 weights of one group (g % 32 == 0): one 16-byte load of nibbles, its one
+// scale, nibble - 8 -> fp32, a plain fp32 multiply, v_cvt_f16_f32, four 16-byte stores.  A region
+// base that is not 16-byte aligned takes the same schedule with scalar loads and stores.
+namespace {
+
+constexpr int kPer4 = 32;
+constexpr int kTail4 = kPer4 * kThreads;
+
+struct Seg4 {
+  uint64_t a, b, p_off, s_off, k0, ng;
+};
+
+// scale k of a segment whose scales start at byte `off` of the region; dt 0 fp16, 1 bf16, 2 fp32.
+// 2-byte loads only when the region base is not 16-byte aligned (an fp32 scale may then sit at an
+// address that is no multiple of 4).
+template <bool VEC>
+__device__ __forceinline__ float load_scale(const uint8_t* region, uint64_t off, uint64_t idx, int dt) {
+  if (dt == 2) {
+    const uint8_t* p = region + off + idx * 4;
+    if (VEC) return *(const float*)p;
+    const uint32_t lo = *(const uint16_t*)p, hi = *(const uint16_t*)(p + 2);
+    return __uint_as_float(lo | (hi << 16));
+  }
+  const uint16_t h = *(const uint16_t*)(region + off + idx * 2);
+  if (dt == 1) return __uint_as_float((uint32_t)h << 16);
+  return (float)__builtin_bit_cast(half_t, h);
+}
+
+// this launch expands elements [a, a + cnt), cnt % 32 == 0; their nibbles start at byte p_off.  Groups
+// [k0, k_next) have their scales at s_off; group k_next (the one that straddles a + cnt) at s_next.
+// TAIL: one block, cnt <= kTail4, every read completes before any write (the ranges overlap).
+template <bool VEC, bool TAIL>
+__global__ __launch_bounds__(kThreads) void dequant_int4_kernel(uint8_t* region, uint64_t a, uint64_t cnt,
+                                                                uint64_t p_off, uint64_t s_off, uint64_t k0,
+                                                                uint64_t k_next, uint64_t s_next, uint64_t g,
+                                                                int dt) {
+  const uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  const uint64_t off = t * kPer4;
+  const bool active = off < cnt;
+  if (!TAIL && !active) return;
+  half_t o[kPer4];
+  if (active) {
+    uint32_t w[4];
+    const uint8_t* src = region + p_off + off / 2;
+    if (VEC) {
+      const uint4 v = *(const uint4*)src;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) |
+               ((uint32_t)src[4 * j + 3] << 24);
+    }
+    const uint64_t k = (a + off) / g;
+    const float s = k < k_next ? load_scale<VEC>(region, s_off, k - k0, dt) : load_scale<VEC>(region, s_next, 0, dt);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const int q = (int)((w[j] >> (4 * b)) & 15u) - 8;
+        o[8 * j + b] = to_half((float)q * s);
+      }
+  }
+  if (TAIL) __syncthreads();
+  if (!active) return;
+  half_t* dst = (half_t*)region + a + off;
+  if (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      half8 v;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) v[b] = o[8 * j + b];
+      *(half8*)(dst + 8 * j) = v;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kPer4; ++j) dst[j] = o[j];
+  }
+}
+
+// int4.region_layout(): the segments from the top of the region down, i.e. in REVERSE launch order.
+// Returns the count (0 for bad arguments: more than kMaxSeg4 cannot happen below 2^63 weights).
+constexpr int kMaxSeg4 = 64;
+inline int layout4(uint64_t n, uint64_t g, uint64_t es, Seg4* out) {
+  int c = 0;
+  uint64_t top = 2 * n, b = n, a = n <= (uint64_t)kTail4 ? 0 : n - kTail4;
+  while (true) {
+    if (c == kMaxSeg4) return 0;
+    const uint64_t k0 = a / g, k1 = b / g;
+    const uint64_t p_off = top - (b - a) / 2;
+    const uint64_t s_off = (p_off - (k1 - k0) * es) & ~(uint64_t)15;
+    out[c++] = Seg4{a, b, p_off, s_off, k0, k1 - k0};
+    if (a == 0) break;
+    top = s_off;
+    b = a;
+    // cnt / 2 nibble bytes, at most cnt / g + 1 scales and 15 bytes of alignment fit above the front 2b
+    const uint64_t avail = top - 2 * b;
+    if (avail <= es + 15) return 0;
+    const uint64_t cnt = (avail - es - 15) * 2 * g / (g + 2 * es) / kPer4 * kPer4;
+    if (cnt == 0) return 0;
+    a = cnt >= b ? 0 : b - cnt;
+  }
+  return c;
+}
+
+inline bool args4_ok(uint64_t n, uint64_t group, int es) {
+  return group != 0 && group % 32 == 0 && n % group == 0 && (es == 2 || es == 4) && n < (1ull << 60);
+}
+
+}  // namespace
+
+extern "C" int fls_dequant_int4_tail(void) { return kTail4; }
+
+// launches fls_dequant_int4 enqueues for a tensor of n weights in groups of `group` with scales of
+// scale_es bytes (-1: bad arguments)
+extern "C" int fls_dequant_int4_launches(uint64_t n, uint64_t group, int scale_es) {
+  if (!args4_ok(n, group, scale_es)) return -1;
+  if (n == 0) return 0;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, (uint64_t)scale_es, segs);
+  return c > 0 ? c : -1;
+}
+
+// launch j (0 .. launches - 1) of that chain, for tests of the mirror: out = {a, b, packed offset,
+// scale offset, first group, groups}.  0, or -1 for bad arguments or j
+extern "C" int fls_dequant_int4_segment(uint64_t n, uint64_t group, int scale_es, int j, uint64_t* out) {
+  if (!out || n == 0 || !args4_ok(n, group, scale_es)) return -1;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, (uint64_t)scale_es, segs);
+  if (c <= 0 || j < 0 || j >= c) return -1;
+  const Seg4& s = segs[c - 1 - j];
+  out[0] = s.a; out[1] = s.b; out[2] = s.p_off; out[3] = s.s_off; out[4] = s.k0; out[5] = s.ng;
+  return 0;
+}
+
+extern "C" int fls_dequant_int4(void* region, uint64_t n, uint64_t group, int scale_dtype, fls_stream_t s) {
+  if (n == 0) return 0;
+  if (!region || ((uintptr_t)region & 1)) return (int)hipErrorInvalidValue;
+  if (scale_dtype < 0 || scale_dtype > 2) return (int)hipErrorInvalidValue;
+  const int es = scale_dtype == 2 ? 4 : 2;
+  if (!args4_ok(n, group, es)) return (int)hipErrorInvalidValue;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, (uint64_t)es, segs);
+  if (c <= 0) return (int)hipErrorInvalidValue;
+  const bool vec = ((uintptr_t)region & 15) == 0;
+  auto st = (hipStream_t)s;
+  auto* r = (uint8_t*)region;
+  for (int j = c - 1; j >= 0; --j) {      // launch order: from the bottom segment to the tail
+    const Seg4& g4 = segs[j];
+    // the straddling group g4.b / group: the first scale of the next segment (towards the tail) that has any
+    uint64_t s_next = 0;
+    for (int i = j - 1; i >= 0; --i)
+      if (segs[i].ng) { s_next = segs[i].s_off; break; }
+    const uint64_t cnt = g4.b - g4.a, k_next = g4.k0 + g4.ng;
+    const uint64_t blocks = (cnt / kPer4 + kThreads - 1) / kThreads;
+    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    if (j == 0) {      // cnt <= kTail4: one block
+      if (vec)
+        hipLaunchKernelGGL((dequant_int4_kernel<true, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off, g4.k0, k_next, s_next, group, scale_dtype);
+      else
+        hipLaunchKernelGGL((dequant_int4_kernel<false, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off, g4.k0, k_next, s_next, group, scale_dtype);
+    } else {
+      if (vec)
+        hipLaunchKernelGGL((dequant_int4_kernel<true, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off, g4.k0, k_next, s_next, group, scale_dtype);
+      else
+        hipLaunchKernelGGL((dequant_int4_kernel<false, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off, g4.k0, k_next, s_next, group, scale_dtype);
+    }
+    FLS_CHECK_LAUNCH();
+  }
+  return 0;
+}

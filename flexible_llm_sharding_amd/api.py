@@ -65,9 +65,9 @@ def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str
     if mode in ("disk", "stream"):
         return "stream"
     need = 0
-    if source is not None and not sliced and source.fp8_tensors():
-        # an FP8 checkpoint is pinned as its file bytes (runtime.weights.CompactHostStore), not as
-        # the fp16 image: a 70B FP8 model asks for about 70 GB instead of 138 GB
+    if source is not None and not sliced and (source.fp8_tensors() or source.int4_tensors()):
+        # an FP8 or INT4 checkpoint is pinned as its file bytes (runtime.weights.CompactHostStore), not
+        # as the fp16 image: a 70B FP8 model asks for about 70 GB instead of 138 GB, an INT4 one for 35 GB
         need = source.file_bytes(names)
         names = ()
     for n in names:
@@ -103,9 +103,12 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device):
     if n_fp8 and getattr(args, "verbose", False):
         print(f"FP8 checkpoint: {n_fp8} e4m3 tensors are expanded to fp16 in HBM (weight-only FP8); "
               f"{len(src.ignored_scales())} input_scale tensors are ignored: activations stay fp16", file=sys.stderr)
+    n_int4 = src.int4_tensors()
+    if n_int4 and getattr(args, "verbose", False):
+        print(f"INT4 checkpoint: {n_int4} W4A16 tensors are expanded to fp16 in HBM (weight-only INT4)", file=sys.stderr)
     if resolve_weight_cache(args, cfg, comm, mine, sliced=False, source=src) == "stream":
         return src
-    if n_fp8:
+    if n_fp8 or n_int4:
         # the files' bytes pinned as they are, FP8 as FP8; norms are folded as each layer lands
         from .runtime.weights import CompactHostStore
         return CompactHostStore(src, pinned=device.type == "cuda")
@@ -121,7 +124,11 @@ def check_fp8_dp_shard(args, cfg: ModelConfig) -> None:
     if getattr(args, "synthetic", None) or not getattr(args, "model_path", None):
         return
     names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
-    if FileLayerSource(cfg, args.model_path, names=names).fp8_tensors():
+    src = FileLayerSource(cfg, args.model_path, names=names)
+    if src.int4_tensors():
+        raise ValueError("--dp_weight_shard true does not serve an INT4 checkpoint (its 1/G byte slices cut through "
+                         "tensors): pass --dp_weight_shard false, or run model parallel")
+    if src.fp8_tensors():
         raise ValueError("--dp_weight_shard true does not serve an FP8 checkpoint (its 1/G byte slices cut through "
                          "tensors): pass --dp_weight_shard false, or run model parallel")
 
@@ -671,6 +678,7 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     metrics["weight_file_bytes"] = int(files.file_bytes() if hasattr(files, "file_bytes")
                                        else getattr(src, "total_bytes", 0))
     metrics["fp8_tensors"] = int(files.fp8_tensors()) if hasattr(files, "fp8_tensors") else 0
+    metrics["int4_tensors"] = int(files.int4_tensors()) if hasattr(files, "int4_tensors") else 0
     metrics["weight_pinned_bytes"] = int(src.pinned_bytes() if hasattr(src, "pinned_bytes")
                                          else getattr(src, "total_bytes", 0))
     metrics["score_d2h_bytes_last_pass"] = int(getattr(runner, "score_d2h_bytes", 0))

@@ -1,0 +1,335 @@
+"""Weight-only INT4 (W4A16, symmetric, group-scaled) checkpoints: the host definition.
+
+A 2-D projection weight ``X.weight`` of shape ``[out, in]`` is stored as
+
+    X.weight_packed   I32  [out, in / 8]   element [r, c] is the nibble in bits
+                                           [4 (c % 8), 4 (c % 8) + 4) of word [r, c // 8]; as a
+                                           little-endian byte stream, row-major element i sits in
+                                           byte i // 2, an even i in the low nibble
+    X.weight_scale    fp16 / bf16 / fp32  [out, in / g]   (``[out]`` is ``[out, 1]``: per channel)
+    X.weight_shape    I64  [2] = [out, in]
+
+The nibble ``u`` in 0..15 encodes ``q = u - 8`` (symmetric, offset binary); the group size ``g`` is
+a multiple of 32 that divides ``in``, and element ``[r, c]`` uses scale ``[r, c // g]``.  Its value is
+
+    w16 = fp16_rne( fp32(q) * fp32(scale) )
+
+one fp32 multiply, then one round-to-nearest-even to fp16 (overflow to +-inf; ``0 * negative`` is
+-0).  This is the layout llm-compressor's ``pack-quantized`` W4A16 symmetric scheme is understood
+to write.  ``X.weight_zero_point`` (asymmetric) and ``X.weight_g_idx`` (activation order) are refused.
+
+The *fp16 twin* of an INT4 checkpoint is the same directory with ``X.weight`` written as ``w16`` and
+the three companions removed (:func:`write_twin`): a run on the INT4 checkpoint gives, bit for bit,
+the outputs of the same run on its twin.
+
+Landing layout (:func:`region_layout`).  A tensor of ``N`` weights owns its ``2N``-byte region of
+the layer image and nothing else.  ``fls_dequant_int4`` (``csrc/kernels/dequant.hip``) expands
+elements ``[a, b)`` per stream-ordered launch, writing bytes ``[2a, 2b)``; a launch must not write a
+byte that is still unread.  Packed bytes and scales both have to approach the top of the region as
+the element index approaches ``N``, which two contiguous blocks cannot do, so the inputs land
+*segment by segment*, one segment per launch, stacked downwards from the top of the region in
+reverse launch order:
+
+    [ ... free ... | scales_0 | packed_0 | scales_1 | packed_1 | ... | scales_tail | packed_tail ]
+
+``packed_j`` are the ``(b_j - a_j) / 2`` packed bytes of launch ``j``, ``scales_j`` the raw scale
+bytes (file dtype) of the groups that *end* in ``[a_j, b_j)``, at a 16-byte aligned offset.  A group
+that straddles a launch boundary is read by the earlier launch from the later segment, which lies
+above it.  Launch ``j`` may run because ``2 b_j <= offset(scales_j)``: everything unread lies at or
+above its own segment.  The segments are sized from the top: the tail holds at most ``TAIL``
+weights, which one block reads into registers before a barrier and then writes; every segment
+below takes as many weights as fit under the rule, about ``1 / (1/4 + es / 2g)`` times what lies
+above it, so the chain is about ``log(N / TAIL) / log(3.2 .. 3.9)`` launches.
+"""
+from __future__ import annotations
+
+import functools
+import glob
+import os
+import shutil
+from typing import Dict, List, NamedTuple, Sequence, Tuple
+
+import torch
+
+from .fp8 import is_quantized_name
+
+PER_THREAD = 32                    # weights per kernel thread: one 16-byte load of nibbles
+TAIL = PER_THREAD * 256            # weights the final single-block launch can hold
+SCALE_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+SCALE_CODES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}     # fls_dequant_int4's scale_dtype
+PACKED, SCALE, SHAPE = ".weight_packed", ".weight_scale", ".weight_shape"
+REFUSED = {"_zero_point": "a zero point (asymmetric quantisation)",        # after "X.weight"
+           "_g_idx": "a group index (activation ordering)"}
+
+
+# ------------------------------------------------------------------------------- the value
+def unpack(packed: torch.Tensor) -> torch.Tensor:
+    """``q`` (int8, -8..7) of shape ``[out, in]`` from int32 words ``[out, in / 8]``."""
+    if packed.dtype != torch.int32 or packed.dim() != 2:
+        raise TypeError(f"INT4 words are 2-D int32, got {packed.dtype} {tuple(packed.shape)}")
+    by = packed.detach().to("cpu").contiguous().view(torch.uint8)          # (little-endian host: byte i // 2)
+    u = torch.stack((by & 15, by >> 4), -1).reshape(packed.shape[0], packed.shape[1] * 8)
+    return u.to(torch.int8) - 8
+
+
+def pack(q: torch.Tensor) -> torch.Tensor:
+    """int32 words ``[out, in / 8]`` of the values ``q`` in -8..7 of shape ``[out, in]``."""
+    if q.dim() != 2 or q.shape[1] % 8:
+        raise ValueError(f"INT4 weights are 2-D with in % 8 == 0, got shape {tuple(q.shape)}")
+    v = q.detach().to("cpu")
+    if v.numel() and (int(v.min()) < -8 or int(v.max()) > 7):
+        raise ValueError("INT4 values lie in -8..7")
+    u = (v.to(torch.int16) + 8).to(torch.uint8).reshape(q.shape[0], -1, 2)
+    by = (u[..., 0] | (u[..., 1] << 4)).contiguous()                        # (little-endian host: byte i // 2)
+    return by.view(torch.int32)
+
+
+def group_size(scale_shape: Sequence[int], weight_shape: Sequence[int]) -> int:
+    """The group size ``g`` a scale of ``scale_shape`` gives an ``[out, in]`` weight; ValueError if
+    none (``g`` is a multiple of 32 that divides ``in``)."""
+    ss, ws = tuple(scale_shape), tuple(weight_shape)
+    if len(ws) != 2:
+        raise ValueError(f"INT4 weights are 2-D, got shape {ws}")
+    out, inn = ws
+    if ss == (out,):
+        ss = (out, 1)
+    if len(ss) != 2 or ss[0] != out or ss[1] < 1 or inn % ss[1] or (inn // ss[1]) % 32:
+        raise ValueError(f"scale shape {tuple(scale_shape)} gives a {ws} weight no group size that is a "
+                         "multiple of 32 dividing its row length")
+    return inn // ss[1]
+
+
+def dequantize(packed: torch.Tensor, scale: torch.Tensor, shape: Sequence[int]) -> torch.Tensor:
+    """``w16`` of shape ``shape`` = ``[out, in]`` from the int32 words and the group scales."""
+    out, inn = (int(x) for x in shape)
+    if tuple(packed.shape) != (out, inn // 8) or inn % 8:
+        raise ValueError(f"INT4 words of a [{out}, {inn}] weight have shape [{out}, {inn // 8}], got "
+                         f"{tuple(packed.shape)}")
+    if scale.dtype not in SCALE_DTYPES:
+        raise TypeError(f"INT4 scales are fp16 / bf16 / fp32, got {scale.dtype}")
+    g = group_size(tuple(scale.shape), (out, inn))
+    s = scale.detach().to("cpu").to(torch.float32).reshape(out, inn // g, 1)
+    q = unpack(packed).to(torch.float32).reshape(out, inn // g, g)
+    return (q * s).to(torch.float16).reshape(out, inn)
+
+
+def quantize(w: torch.Tensor, group: int = 128, scale_dtype: torch.dtype = torch.float16):
+    """``(packed int32 [out, in / 8], scale scale_dtype [out, in / g])``.  Per group
+    ``s = scale_dtype(amax / 7)``, replaced by 1 where it is 0 and by the largest finite value where
+    it overflowed; ``q = clamp(round_half_even(fp32(w) / fp32(s)), -8, 7)``.  Where the rounding of
+    ``s`` went up far enough that ``7 s`` would round to inf in fp16 (amax 65504 with fp16 scales:
+    ``s`` = 9360, ``7 s`` = 65520), ``s`` is the next lower value of its dtype instead, so the
+    largest weight of a finite fp16 group stays finite.  ``group <= 0``: one scale per output
+    channel (``g = in``)."""
+    if w.dim() != 2:
+        raise ValueError(f"INT4 weights are 2-D, got shape {tuple(w.shape)}")
+    if scale_dtype not in SCALE_DTYPES:
+        raise TypeError(f"INT4 scales are fp16 / bf16 / fp32, got {scale_dtype}")
+    out, inn = w.shape
+    g = inn if group <= 0 else int(group)
+    if g % 32 or inn % g:
+        raise ValueError(f"--int4_group {g}: a multiple of 32 that divides the row length {inn}")
+    f = w.detach().to("cpu").to(torch.float32).reshape(out, inn // g, g)
+    s = (f.abs().amax(-1) / 7.0).to(scale_dtype)
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    s = torch.where(torch.isinf(s), torch.full_like(s, torch.finfo(scale_dtype).max), s)
+    over = torch.isinf((s.to(torch.float32) * 7.0).to(torch.float16))
+    if bool(over.any()):
+        bits = torch.int32 if scale_dtype == torch.float32 else torch.int16
+        s = torch.where(over, (s.view(bits) - 1).view(scale_dtype), s)      # (s > 0: the next lower value)
+    q = torch.clamp(torch.round(f / s.to(torch.float32).unsqueeze(-1)), -8, 7)
+    return pack(q.reshape(out, inn).to(torch.int8)), s.contiguous()
+
+
+# --------------------------------------------------------------------------- names
+def is_companion_name(name: str) -> bool:
+    """A tensor that belongs to an INT4 weight: its words, its scales or its shape."""
+    return name.endswith((PACKED, SCALE, SHAPE))
+
+
+def weight_of_companion(name: str) -> str:
+    """``X.weight`` for ``X.weight_packed`` / ``X.weight_scale`` / ``X.weight_shape``."""
+    for suf in (PACKED, SCALE, SHAPE):
+        if name.endswith(suf):
+            return name[:-len(suf)] + ".weight"
+    raise ValueError(name)
+
+
+def packed_name(weight_name: str) -> str:
+    return weight_name + "_packed"
+
+
+def is_packed_source(weight_name: str, available) -> bool:
+    """``weight_name`` is not in the checkpoint itself but its INT4 words are."""
+    return weight_name not in available and packed_name(weight_name) in available
+
+
+def check_entry(weight_name: str, infos, shape: Sequence[int], where: str = "") -> Tuple[str, str, str, int]:
+    """Validate the tensors of INT4 weight ``weight_name`` whose placement has ``shape``.  ``infos``
+    maps names to objects with ``dtype`` and ``shape`` (tensors, or safetensors header entries).
+    Returns ``(packed name, scale name, shape name, g)``; TypeError naming the tensor otherwise.  The
+    *contents* of ``X.weight_shape`` are the caller's to compare (:func:`check_shape_values`)."""
+    pk, sk, hk = weight_name + "_packed", weight_name + "_scale", weight_name + "_shape"
+    what = f"{where}{weight_name} (INT4)"
+    for suf, why in REFUSED.items():
+        if weight_name + suf in infos:
+            raise TypeError(f"{what} has {why}, {weight_name + suf}; only symmetric, in-order group "
+                            "quantisation is supported")
+    if len(tuple(shape)) != 2:
+        raise TypeError(f"{what}: only 2-D projection weights may be INT4, this one has shape {tuple(shape)}")
+    out, inn = shape
+    p = infos[pk]
+    if p.dtype != torch.int32:
+        raise TypeError(f"{what}: {pk} has dtype {p.dtype}; INT4 words are I32 (eight nibbles per word)")
+    if inn % 8 or tuple(p.shape) != (out, inn // 8):
+        raise TypeError(f"{what}: {pk} has shape {tuple(p.shape)}, a [{out}, {inn}] weight packs to "
+                        f"[{out}, {inn // 8}] (4 bits per weight)")
+    if hk not in infos:
+        raise TypeError(f"{what} has no {hk}")
+    h = infos[hk]
+    if h.dtype != torch.int64 or tuple(h.shape) != (2,):
+        raise TypeError(f"{what}: {hk} is {h.dtype} {tuple(h.shape)}, not I64 [2]")
+    if sk not in infos:
+        raise TypeError(f"{what} has no scale tensor {sk}")
+    s = infos[sk]
+    if s.dtype not in SCALE_DTYPES:
+        raise TypeError(f"{what}: {sk} has dtype {s.dtype}; INT4 scales are fp16 / bf16 / fp32")
+    try:
+        g = group_size(tuple(s.shape), (out, inn))
+    except ValueError as e:
+        raise TypeError(f"{what}: {sk} {e}") from None
+    return pk, sk, hk, g
+
+
+def check_shape_values(weight_name: str, values: Sequence[int], shape: Sequence[int], where: str = "") -> None:
+    if tuple(int(v) for v in values) != tuple(shape):
+        raise TypeError(f"{where}{weight_name} (INT4): weight_shape is {[int(v) for v in values]}, the model "
+                        f"expects {list(shape)}")
+
+
+def dequantize_entry(sd: Dict[str, torch.Tensor], weight_name: str, shape: Sequence[int], where: str = "") -> torch.Tensor:
+    """``w16`` of INT4 weight ``weight_name`` of a state dict, validated against ``shape``."""
+    pk, sk, hk, _ = check_entry(weight_name, sd, shape, where)
+    check_shape_values(weight_name, sd[hk].tolist(), shape, where)
+    return dequantize(sd[pk], sd[sk], shape)
+
+
+# --------------------------------------------------------------------------- converter
+def quantize_state_dict(sd: Dict[str, torch.Tensor], group: int = 128,
+                        scale_dtype: torch.dtype = torch.float16) -> Dict[str, torch.Tensor]:
+    """``--quantize int4`` of one file's tensors: every 2-D projection weight
+    (``fp8.is_quantized_name``) of a float dtype becomes the three companions; everything else,
+    the companions of a checkpoint that is INT4 already included, passes through."""
+    out = {}
+    for k, v in sd.items():
+        if is_quantized_name(k) and v.dim() == 2 and v.dtype in (torch.float16, torch.bfloat16, torch.float32):
+            packed, scale = quantize(v, group, scale_dtype)
+            out[k + "_packed"] = packed
+            out[k + "_scale"] = scale
+            out[k + "_shape"] = torch.tensor(list(v.shape), dtype=torch.int64)
+        else:
+            out[k] = v
+    return out
+
+
+def dequantize_state_dict(sd: Dict[str, torch.Tensor], where: str = "") -> Dict[str, torch.Tensor]:
+    """The twin of one file's tensors: ``X.weight`` = ``w16`` in the place of ``X.weight_packed``,
+    the scale and shape tensors dropped."""
+    out = {}
+    for k, v in sd.items():
+        if k.endswith(PACKED):
+            w = weight_of_companion(k)
+            if w + "_shape" not in sd:
+                raise TypeError(f"{where}{w} (INT4) has no {w}_shape")
+            out[w] = dequantize_entry(sd, w, tuple(int(x) for x in sd[w + "_shape"].tolist()), where)
+        elif k.endswith((SCALE, SHAPE)) and packed_name(weight_of_companion(k)) in sd:
+            continue
+        else:
+            out[k] = v
+    return out
+
+
+def write_twin(src_dir: str, dst_dir: str) -> None:
+    """Write the fp16 twin of the checkpoint directory ``src_dir`` to ``dst_dir``."""
+    from .utils.safetensors_io import load_file, save_file
+    os.makedirs(dst_dir, exist_ok=True)
+    for fn in sorted(glob.glob(os.path.join(src_dir, "*"))):
+        base = os.path.basename(fn)
+        if os.path.isdir(fn):
+            continue
+        if base.endswith(".safetensors"):
+            save_file(dequantize_state_dict(load_file(fn), base + ": "), os.path.join(dst_dir, base))
+        else:
+            shutil.copy(fn, os.path.join(dst_dir, base))
+
+
+# --------------------------------------------------------------------------- landing layout
+class Segment(NamedTuple):
+    """One launch: elements ``[a, b)``; their packed bytes at region offset ``packed_off``; the
+    ``n_groups`` scales of groups ``first_group ...`` (those that end in ``[a, b)``) at ``scale_off``."""
+    a: int
+    b: int
+    packed_off: int
+    scale_off: int
+    first_group: int
+    n_groups: int
+
+
+def _check(n: int, g: int, scale_es: int) -> None:
+    if scale_es not in (2, 4):
+        raise ValueError(f"INT4 scales have 2 or 4 bytes, not {scale_es}")
+    if g <= 0 or g % 32 or n < 0 or n % g:
+        raise ValueError(f"INT4: group {g} must be a multiple of 32 that divides the {n} weights")
+
+
+@functools.lru_cache(maxsize=256)
+def region_layout(n: int, g: int, scale_es: int) -> Tuple[Segment, ...]:
+    """The segments of a tensor of ``n`` weights in launch order (see the module docstring).  Built
+    from the top of the ``2n``-byte region: the tail first, then each earlier launch as large as
+    ``2 b <= scale_off`` allows.  The host code of ``fls_dequant_int4`` mirrors this function."""
+    _check(n, g, scale_es)
+    segs: List[Segment] = []
+    if n == 0:
+        return ()
+    top, b = 2 * n, n
+    a = 0 if n <= TAIL else n - TAIL
+    while True:
+        k0, k1 = a // g, b // g
+        p_off = top - (b - a) // 2
+        s_off = (p_off - (k1 - k0) * scale_es) & ~15
+        segs.append(Segment(a, b, p_off, s_off, k0, k1 - k0))
+        if a == 0:
+            break
+        top, b = s_off, a
+        # the next lower launch takes cnt weights: cnt / 2 packed bytes, at most cnt / g + 1 scales
+        # and up to 15 bytes of alignment must fit between the write front 2b and `top`
+        avail = top - 2 * b
+        cnt = (avail - scale_es - 15) * 2 * g // (g + 2 * scale_es) // PER_THREAD * PER_THREAD
+        if cnt <= 0:
+            raise AssertionError("INT4 landing layout made no progress")
+        a = max(0, b - cnt)
+    return tuple(reversed(segs))
+
+
+def schedule(n: int, g: int, scale_es: int) -> List[Tuple[int, int]]:
+    """The ``[a, b)`` element ranges of the launches of ``fls_dequant_int4``, in order."""
+    return [(s.a, s.b) for s in region_layout(n, g, scale_es)]
+
+
+def landing_span(n: int, g: int, scale_es: int) -> Tuple[int, int]:
+    """``(offset, bytes)`` of the part of the region the landed inputs occupy: from the first
+    segment's scales to the end of the region."""
+    lay = region_layout(n, g, scale_es)
+    return (lay[0].scale_off, 2 * n - lay[0].scale_off) if lay else (0, 0)
+
+
+def land(region: torch.Tensor, packed_bytes: torch.Tensor, scale_bytes: torch.Tensor, n: int, g: int,
+         scale_es: int) -> None:
+    """Place a tensor's packed bytes (``n / 2``) and raw scale bytes into the uint8 ``region`` the way
+    the loader does (tests, benchmarks)."""
+    for s in region_layout(n, g, scale_es):
+        region[s.packed_off:s.packed_off + (s.b - s.a) // 2].copy_(packed_bytes[s.a // 2:s.b // 2])
+        if s.n_groups:
+            region[s.scale_off:s.scale_off + s.n_groups * scale_es].copy_(
+                scale_bytes[s.first_group * scale_es:(s.first_group + s.n_groups) * scale_es])
+

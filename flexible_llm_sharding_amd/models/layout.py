@@ -259,9 +259,16 @@ def _expert_placements(cfg: ModelConfig, p: str, o: Dict[str, int], es: int) -> 
 
 
 def source_key(cfg: ModelConfig, layer_name: str, hf_name: str, available) -> str:
-    """Checkpoint key that feeds ``hf_name`` (tied LM head: the embedding table)."""
+    """Checkpoint key that feeds ``hf_name`` (tied LM head: the embedding table; a weight of an
+    INT4 checkpoint: its ``X.weight_packed`` words, int4.py)."""
+    from ..int4 import is_packed_source, packed_name
     if hf_name in available:
+        if packed_name(hf_name) in available:
+            raise TypeError(f"{layer_name}: {hf_name} is stored twice, as itself and as INT4 words "
+                            f"({packed_name(hf_name)}); a layer file holds one of the two")
         return hf_name
+    if is_packed_source(hf_name, available):
+        return packed_name(hf_name)
     if hf_name == "lm_head.weight" and cfg.tie_word_embeddings and "model.embed_tokens.weight" in available:
         return "model.embed_tokens.weight"
     raise KeyError(f"{layer_name}: missing tensor {hf_name}")
@@ -275,10 +282,13 @@ def check_layer_tensors(cfg: ModelConfig, layer_name: str, available) -> None:
     if cfg.model_type in SUPPORTED_MODEL_TYPES:
         return
     from ..fp8 import is_scale_name, weight_of_scale
+    from ..int4 import is_companion_name, weight_of_companion
     want = {pl.hf_name for pl in placements(cfg, layer_name)}
-    # (the scale tensors of an FP8 checkpoint follow their weight: fp8.py)
+    # (the scale tensors of an FP8 checkpoint follow their weight: fp8.py; so do the words, scales
+    # and shape of an INT4 weight: int4.py)
     extra = sorted(k for k in available if k not in want and not k.endswith("rotary_emb.inv_freq")
-                   and not (is_scale_name(k) and weight_of_scale(k) in want))
+                   and not (is_scale_name(k) and weight_of_scale(k) in want)
+                   and not (is_companion_name(k) and weight_of_companion(k) in want))
     if extra:
         raise NotImplementedError(f"model_type={cfg.model_type!r} runs as Llama, but {layer_name} holds tensors a "
                                   f"Llama layer does not have: {extra[:4]}")
@@ -309,7 +319,11 @@ def pack_layer(cfg: ModelConfig, layer_name: str, sd: Dict[str, torch.Tensor],
     b = out.view(torch.uint8)
     for pl in placements(cfg, layer_name, es):
         key = source_key(cfg, layer_name, pl.hf_name, sd)
-        t = sd[key]
+        if key != pl.hf_name and key == pl.hf_name + "_packed":
+            from .. import int4             # weight-only INT4: the image holds w16 (int4.py)
+            t = int4.dequantize_entry(sd, pl.hf_name, pl.shape, f"{layer_name}: ")
+        else:
+            t = sd[key]
         if tuple(t.shape) != pl.shape:
             raise ValueError(f"{layer_name}: {key} has shape {tuple(t.shape)}, config expects {pl.shape}")
         if t.dtype == torch.float8_e4m3fn:

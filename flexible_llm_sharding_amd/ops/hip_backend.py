@@ -710,6 +710,19 @@ class HipOps:
         _chk(self.k.fls_dequant_fp8(region.data_ptr(), numel, scale.data_ptr(), kind, cols, _stream()),
              "fls_dequant_fp8")
 
+    def dequant_int4(self, region: torch.Tensor, numel: int, group: int, scale_dtype: torch.dtype) -> None:
+        """Expand the INT4 tensor of ``numel`` weights that landed in its ``2 * numel``-byte ``region``
+        (int4.region_layout) to fp16 in place (int4.py's definition; csrc/kernels/dequant.hip)."""
+        from ..int4 import SCALE_CODES
+        if region.numel() * region.element_size() != 2 * numel or not region.is_contiguous():
+            raise ValueError("the region of an INT4 tensor is 2 bytes per weight")
+        if scale_dtype not in SCALE_CODES:
+            raise TypeError(f"INT4 scales are fp16 / bf16 / fp32, got {scale_dtype}")
+        if group <= 0 or group % 32 or numel % group:
+            raise ValueError(f"INT4 group {group} is no multiple of 32 that divides {numel} weights")
+        _chk(self.k.fls_dequant_int4(region.data_ptr(), numel, group, SCALE_CODES[scale_dtype], _stream()),
+             "fls_dequant_int4")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -345,6 +345,27 @@ class TorchOps:
         w = fp8.dequantize(b[numel:].to("cpu").clone().view(rows, cols), s)
         b.view(torch.float16).copy_(w.reshape(-1))
 
+    def dequant_int4(self, region: torch.Tensor, numel: int, group: int, scale_dtype: torch.dtype) -> None:
+        """The INT4 tensor of ``numel`` weights that landed in its ``2 * numel``-byte ``region``
+        (int4.region_layout) -> fp16 in place, by the host definition (int4.dequantize)."""
+        from .. import int4
+        b = region.view(torch.uint8)
+        if b.numel() != 2 * numel:
+            raise ValueError("the region of an INT4 tensor is 2 bytes per weight")
+        if numel == 0:
+            return
+        es = torch.empty((), dtype=scale_dtype).element_size()
+        host = b.to("cpu")
+        words = torch.empty(numel // 2, dtype=torch.uint8)
+        scales = torch.empty(numel // group * es, dtype=torch.uint8)
+        for s in int4.region_layout(numel, group, es):
+            words[s.a // 2:s.b // 2] = host[s.packed_off:s.packed_off + (s.b - s.a) // 2]
+            scales[s.first_group * es:(s.first_group + s.n_groups) * es] = host[s.scale_off:s.scale_off + s.n_groups * es]
+        rows = numel // group                      # (one row per group: the value depends on nothing else)
+        w = int4.dequantize(words.view(torch.int32).view(rows, group // 8), scales.view(scale_dtype).view(rows, 1),
+                            (rows, group))
+        b.view(torch.float16).copy_(w.reshape(-1))
+
     # ------------------------------------------------------- synthetic init
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         """Random-init one packed layer in place (norm weights ~ 1, embeddings ~ N(0,1))."""

@@ -22,7 +22,11 @@ Here the same small-RAM envelope costs no CPU work per pass:
 * FP8 (e4m3fn) tensors of a weight-only FP8 checkpoint (:mod:`..fp8`) are read and copied as
   they are, one byte per weight, into the upper half of the tensor's own region of the image,
   and expanded to fp16 in place there by ``fls_dequant_fp8`` on the copy stream, scaled by the
-  tensor's scales (read once at plan time, resident on the device in one arena per source).
+  tensor's scales (read once at plan time, resident on the device in one arena per source);
+* INT4 tensors of a weight-only W4A16 checkpoint (:mod:`..int4`) are read and copied as they are,
+  nibbles and raw group scales, segment by segment into the top of the tensor's own region of the
+  image (``int4.region_layout``) and expanded to fp16 in place there by ``fls_dequant_int4`` on the
+  copy stream; the scales travel with the weights and take no device memory of their own.
 
 Data-parallel ranks stream only their 1/G byte range of the packed image
 (:meth:`LayerPlan.pieces`) and complete the layer with an RCCL all-gather
@@ -40,7 +44,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, fp8, knobs
+from .. import _native, fp8, int4, knobs
 from ..config import ModelConfig
 from ..models.layout import check_layer_tensors, layer_kind, layer_layout, placements, source_key
 from ..utils.layer_format import layer_file
@@ -60,7 +64,11 @@ class TensorRun:
     An FP8 tensor (``src_es`` 1, weight-only FP8: :mod:`..fp8`) lands as raw bytes in the upper
     half ``[img_off + numel, img_off + 2 * numel)`` of its region and is expanded to fp16 in place
     there; ``scale`` is its flat fp32 scale (read at plan time), ``scale_kind`` one of
-    ``fp8.KIND_*``, ``cols`` the tensor's row length."""
+    ``fp8.KIND_*``, ``cols`` the tensor's row length.
+
+    An INT4 tensor (``group`` > 0, weight-only W4A16: :mod:`..int4`) is ``numel / 2`` bytes of
+    nibbles at ``file_off`` plus ``numel / group`` raw scales of ``scale_dtype`` at ``scale_off`` of
+    the file; both land in the top of the region as ``int4.region_layout`` lays them out."""
     hf_name: str
     file_off: int
     img_off: int
@@ -69,10 +77,38 @@ class TensorRun:
     scale_kind: int = -1
     cols: int = 0
     scale: Optional[torch.Tensor] = field(default=None, compare=False, repr=False)
+    group: int = 0
+    scale_off: int = 0
+    scale_dtype: Optional[torch.dtype] = None
 
     @property
     def src_es(self) -> int:
         return _SRC_ES[self.src_dtype]
+
+    @property
+    def is_int4(self) -> bool:
+        return self.group > 0
+
+    @property
+    def scale_es(self) -> int:
+        return _SRC_ES[self.scale_dtype]
+
+    @property
+    def file_nbytes(self) -> int:
+        """Tensor bytes of the file that a pass reads and copies for this tensor."""
+        if self.is_int4:
+            return self.numel // 2 + self.numel // self.group * self.scale_es
+        return self.numel * self.src_es
+
+    def int4_pieces(self) -> List[Tuple[int, int, int]]:
+        """(file_off, bytes, region offset) of an INT4 tensor's landing pieces: per segment its
+        nibbles and, where it holds any, its scales."""
+        out = []
+        for s in int4.region_layout(self.numel, self.group, self.scale_es):
+            if s.n_groups:
+                out.append((self.scale_off + s.first_group * self.scale_es, s.n_groups * self.scale_es, s.scale_off))
+            out.append((self.file_off + s.a // 2, (s.b - s.a) // 2, s.packed_off))
+        return out
 
     @property
     def is_fp8(self) -> bool:
@@ -97,6 +133,9 @@ class LayerPlan:
         runs = []
         for pl in placements(cfg, layer_name):
             key = source_key(cfg, layer_name, pl.hf_name, infos)
+            if key != pl.hf_name and key == int4.packed_name(pl.hf_name):
+                runs.append(self._int4_run(path, pl, infos))
+                continue
             ti: TensorInfo = infos[key]
             if ti.dtype == torch.int8:
                 raise AssertionError("int8 not supported (need to add fp16_statistics)")   # utils.py:129
@@ -113,9 +152,11 @@ class LayerPlan:
                 runs.append(TensorRun(key, ti.begin, pl.offset, pl.numel, ti.dtype))
         self.runs = sorted(runs, key=lambda r: r.file_off)
         self.nbytes = layer_layout(cfg, layer_kind(layer_name)).nbytes
-        # bytes of the file's tensors that a pass reads and copies (FP8 tensors: 1 per weight)
-        self.file_bytes = sum(r.numel * r.src_es for r in self.runs)
+        # bytes of the file's tensors that a pass reads and copies (FP8 tensors: 1 per weight; INT4
+        # tensors: half a byte per weight plus the scales)
+        self.file_bytes = sum(r.file_nbytes for r in self.runs)
         self.fp8_tensors = sum(1 for r in self.runs if r.is_fp8)
+        self.int4_tensors = sum(1 for r in self.runs if r.is_int4)
         self.ignored_scales = sorted(k for k in infos if k.endswith(".input_scale"))
 
     @staticmethod
@@ -134,6 +175,21 @@ class LayerPlan:
         scale = raw.view(si.dtype).to(torch.float32).reshape(-1).contiguous()
         return TensorRun(key, ti.begin, pl.offset, pl.numel, ti.dtype, kind, pl.shape[1], scale)
 
+    @staticmethod
+    def _int4_run(path: str, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
+        """The run of the INT4 tensor that feeds placement ``pl``.  Only ``X.weight_shape`` (16 bytes)
+        is read now; the scales are read with the weights, every pass."""
+        where = f"{path}: "
+        pk, sk, hk, g = int4.check_entry(pl.hf_name, infos, pl.shape, where)
+        raw = torch.empty(16, dtype=torch.uint8)
+        hostmem.pread_into(path, infos[hk].begin, 16, raw)
+        int4.check_shape_values(pl.hf_name, raw.view(torch.int64).tolist(), pl.shape, where)
+        ti, si = infos[pk], infos[sk]
+        if ti.nbytes != pl.numel // 2 or si.nbytes != pl.numel // g * _SRC_ES[si.dtype]:
+            raise ValueError(f"{path}: {pk} / {sk} byte sizes do not match their shapes")
+        return TensorRun(pl.hf_name, ti.begin, pl.offset, pl.numel, ti.dtype, group=g, scale_off=si.begin,
+                         scale_dtype=si.dtype)
+
     def pieces(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
         """(file_off, file_bytes, dst_off, kind) covering image bytes [lo, hi); dst_off relative to lo.
         lo / hi must be even (whole fp16 elements)."""
@@ -145,6 +201,12 @@ class LayerPlan:
             a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
             if a >= b:
                 continue
+            if r.is_int4:
+                if (a, b) != (r.img_off, r.img_off + 2 * r.numel):
+                    raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the INT4 tensor "
+                                     f"{r.hf_name} (an INT4 tensor loads whole)")
+                out += [(fo, nb, r.img_off + do - lo, KIND_RAW) for fo, nb, do in r.int4_pieces()]
+                continue
             if r.is_fp8:
                 if (a, b) != (r.img_off, r.img_off + 2 * r.numel):
                     raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the FP8 tensor "
@@ -154,6 +216,8 @@ class LayerPlan:
             e0, e1 = (a - r.img_off) // 2, (b - r.img_off) // 2
             out.append((r.file_off + e0 * r.src_es, (e1 - e0) * r.src_es, a - lo,
                         KIND_F32 if r.src_dtype == torch.float32 else KIND_RAW))
+        if self.int4_tensors:
+            out.sort(key=lambda p: p[0])      # (the streamer reads pieces in file order)
         return out
 
     def bf16_runs(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int]]:
@@ -175,6 +239,13 @@ class LayerPlan:
         hi = self.nbytes if hi is None else hi
         return [(r.img_off - lo, r) for r in self.runs
                 if r.is_fp8 and r.img_off >= lo and r.img_off + 2 * r.numel <= hi]
+
+
+    def int4_runs(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, TensorRun]]:
+        """(region offset relative to lo, run) of the INT4 tensors within [lo, hi)."""
+        hi = self.nbytes if hi is None else hi
+        return [(r.img_off - lo, r) for r in self.runs
+                if r.is_int4 and r.img_off >= lo and r.img_off + 2 * r.numel <= hi]
 
 
 def _relabel_layer(infos: Dict[str, TensorInfo], layer_name: str) -> Dict[str, TensorInfo]:
@@ -264,6 +335,9 @@ class FileLayerSource(LayerSource):
             # FP8 bytes landed in the upper half of the tensor's region: the host definition
             from ..ops import get_ops
             get_ops(torch.device("cpu")).dequant_fp8(b[off:off + 2 * r.numel], r.numel, r.scale, r.scale_kind, r.cols)
+        for off, r in pl.int4_runs(lo, hi):
+            from ..ops import get_ops
+            get_ops(torch.device("cpu")).dequant_int4(b[off:off + 2 * r.numel], r.numel, r.group, r.scale_dtype)
         self.read_bytes += sum(p[1] for p in pieces)
         self.read_seconds += time.perf_counter() - t0
 
@@ -328,11 +402,14 @@ class FileLayerSource(LayerSource):
         """In-place bf16 -> fp16 of the bf16 tensors in image bytes [lo, hi) of ``dst``, whose byte 0
         is image byte ``lo`` (current stream)."""
         pl = self.plan(name)
-        runs, f8 = pl.bf16_runs(lo, hi), pl.fp8_runs(lo, hi)
-        if not runs and not f8:
+        runs, f8, i4 = pl.bf16_runs(lo, hi), pl.fp8_runs(lo, hi), pl.int4_runs(lo, hi)
+        if not runs and not f8 and not i4:
             return
         from ..ops import get_ops
         ops = get_ops(dst.device)
+        for off, r in i4:
+            # INT4 tensors: expanded to fp16 in place in their own regions; the scales landed with them
+            ops.dequant_int4(dst[off:off + 2 * r.numel], r.numel, r.group, r.scale_dtype)
         for off, nb in runs:
             v = dst[off:off + nb]
             ops.cast_f16(v, v, 1)
@@ -386,6 +463,10 @@ class FileLayerSource(LayerSource):
     def fp8_tensors(self) -> int:
         """FP8 tensors among this source's layers (0: a pure fp16 / bf16 / fp32 checkpoint)."""
         return sum(self.plan(n).fp8_tensors for n in self.names)
+
+    def int4_tensors(self) -> int:
+        """INT4 tensors among this source's layers."""
+        return sum(self.plan(n).int4_tensors for n in self.names)
 
     def file_bytes(self, names: Optional[Sequence[str]] = None) -> int:
         """Tensor bytes of the layer files (what a pass reads and copies)."""

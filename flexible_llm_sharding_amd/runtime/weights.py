@@ -15,9 +15,10 @@ Here a source yields the *packed* layer image (see :mod:`..models.layout`):
   (read once), so each shard H2D is one DMA at PCIe line rate
   (``--weight_cache host``).  Also built directly from synthetic random-init
   weights (generated on the GPU and copied down) for the 70B benchmark.
-* :class:`CompactHostStore` — an FP8 checkpoint's file bytes resident in pinned
-  host memory, FP8 as FP8 (half the RAM and PCIe bytes), copied tensor by tensor
-  to their landing positions and expanded to fp16 in the HBM slot (:mod:`..fp8`).
+* :class:`CompactHostStore` — an FP8 or INT4 checkpoint's file bytes resident in
+  pinned host memory, FP8 as FP8 (half the RAM and PCIe bytes), INT4 as nibbles
+  and raw scales (a quarter), copied tensor by tensor to their landing positions
+  and expanded to fp16 in the HBM slot (:mod:`..fp8`, :mod:`..int4`).
 * data-parallel scatter-load (:func:`piece_slices`): a rank keeps only its
   1/G byte-slice of every layer piece; the layer (or one piece of it) is
   re-assembled in HBM with an RCCL all-gather over xGMI
@@ -31,7 +32,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native
+from .. import _native, int4
 from ..config import ModelConfig
 from ..models.layout import LayerLayout, layer_kind, layer_layout
 from . import hostmem
@@ -201,7 +202,11 @@ class CompactHostStore(LayerSource):
     as the file source does.  Per layer the tensors sit in file order, each at a
     ``COMPACT_ALIGN``-byte aligned offset; fp32 tensors are kept as fp16.  ``norms_folded`` stays
     False: norms cannot be folded into FP8 bytes without requantising, so they are folded as each
-    layer lands."""
+    layer lands.
+
+    An INT4 tensor (:mod:`..int4`) is pinned as its landing image: the nibbles and raw scales of its
+    segments, each at a 16-byte aligned offset, in the order they take in the tensor's region, so the
+    whole tensor is still one H2D (``int4.landing_span``)."""
 
     norms_folded = False
     COMPACT_ALIGN = 16
@@ -219,6 +224,11 @@ class CompactHostStore(LayerSource):
             offs, off, pieces = {}, 0, []
             for r in pl.runs:
                 offs[r.hf_name] = off
+                if r.is_int4:
+                    base, span = int4.landing_span(r.numel, r.group, r.scale_es)
+                    pieces += [(fo, nb, off + do - base, st.KIND_RAW) for fo, nb, do in r.int4_pieces()]
+                    off += self._aligned(span)
+                    continue
                 f32 = r.src_dtype == torch.float32
                 pieces.append((r.file_off, r.numel * r.src_es, off, st.KIND_F32 if f32 else st.KIND_RAW))
                 off += self._aligned(r.numel * (2 if f32 else r.src_es))
@@ -254,8 +264,8 @@ class CompactHostStore(LayerSource):
         return self.files.plan(name)
 
     def fold_norms(self, device):
-        raise ValueError("--weight_cache host keeps an FP8 checkpoint's bytes as they are in the files: norms "
-                         "cannot be folded into FP8 weights (they are folded as each layer lands)")
+        raise ValueError("--weight_cache host keeps an FP8 or INT4 checkpoint's bytes as they are in the files: norms "
+                         "cannot be folded into quantised weights (they are folded as each layer lands)")
 
     def read_into(self, name: str, dst: torch.Tensor) -> None:
         self.files.read_into(name, dst)
@@ -270,14 +280,17 @@ class CompactHostStore(LayerSource):
         expansions.  Returns the host bytes copied."""
         pl = self.files.plan(name)
         hi = pl.nbytes if hi is None else hi
-        pl.pieces(lo, hi)                   # (refuses a range through an FP8 tensor)
+        pl.pieces(lo, hi)                   # (refuses a range through an FP8 or INT4 tensor)
         buf, offs, total = self.buffers[name], self._offsets[name], 0
         with torch.cuda.stream(stream):
             for r in pl.runs:
                 a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
                 if a >= b:
                     continue
-                if r.is_fp8:
+                if r.is_int4:
+                    base, span = int4.landing_span(r.numel, r.group, r.scale_es)
+                    src, d0 = buf[offs[r.hf_name]:offs[r.hf_name] + span], r.img_off + base - lo
+                elif r.is_fp8:
                     src, d0 = buf[offs[r.hf_name]:offs[r.hf_name] + r.numel], r.land_off - lo
                 else:
                     s0 = offs[r.hf_name] + (a - r.img_off)

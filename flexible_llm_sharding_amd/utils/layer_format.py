@@ -99,15 +99,18 @@ def _load_shard(path: str) -> Dict[str, torch.Tensor]:
 
 
 def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize: str = None,
-                      fp8_scale: str = "channel") -> List[str]:
+                      fp8_scale: str = "channel", int4_group: int = 128, int4_scale_dtype=torch.float16) -> List[str]:
     """Convert an HF checkpoint directory into per-layer safetensors files.
 
     An FP8 (e4m3fn) source checkpoint passes through unchanged: its scale tensors (``weight_scale``,
     ``weight_scale_inv``, ``input_scale``) follow their weight into the layer file.
     ``quantize="fp8"`` writes the decoder layers' projection weights as FP8 with ``fp8_scale``
-    scales (fp8.quantize_state_dict)."""
-    if quantize not in (None, "fp8"):
-        raise ValueError(f"--quantize {quantize!r}: only fp8 is supported")
+    scales (fp8.quantize_state_dict).  An INT4 (W4A16) source checkpoint passes through too, its
+    ``weight_packed`` / ``weight_scale`` / ``weight_shape`` tensors in their weight's layer file;
+    ``quantize="int4"`` writes the same weights as INT4 in groups of ``int4_group`` with
+    ``int4_scale_dtype`` scales (int4.quantize_state_dict)."""
+    if quantize not in (None, "fp8", "int4"):
+        raise ValueError(f"--quantize {quantize!r}: fp8 or int4")
     os.makedirs(out_dir, exist_ok=True)
     for fn in glob.glob(os.path.join(src_dir, "*")):
         base = os.path.basename(fn)
@@ -154,7 +157,10 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
             sd[canonical_param(p)] = cache[wmap[p]][p]
         assert len(sd) == len(layer_params[l]), f"Should have {len(layer_params[l])} keys for {l}"
         out_sd = normalize_expert_names(model_type, sd)
-        if quantize:
+        if quantize == "int4":
+            from ..int4 import quantize_state_dict as quantize_int4
+            out_sd = quantize_int4(out_sd, int4_group, int4_scale_dtype)
+        elif quantize:
             from ..fp8 import quantize_state_dict
             out_sd = quantize_state_dict(out_sd, fp8_scale)
         save_file(out_sd, layer_file(out_dir, l))

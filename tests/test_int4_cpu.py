@@ -1,0 +1,553 @@
+"""Weight-only INT4 (W4A16, group scales) checkpoints without a GPU: the host definition (int4.py)
+against an independent oracle, the quantiser's derived error bound, the landing layout and launch
+schedule (invariants and a launch-by-launch in-place emulation), the loader and stores on the torch
+backend against the fp16 twin, the converter, main.py, and every refusal."""
+import json
+import os
+import pickle
+import socket
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import int4_ref as ir  # noqa: E402
+
+from flexible_llm_sharding_amd import int4  # noqa: E402
+from flexible_llm_sharding_amd.config import preset  # noqa: E402
+from flexible_llm_sharding_amd.engine import ShardedRunner  # noqa: E402
+from flexible_llm_sharding_amd.models.layout import pack_layer, placements  # noqa: E402
+from flexible_llm_sharding_amd.runtime.stream import FileLayerSource, LayerPlan  # noqa: E402
+from flexible_llm_sharding_amd.runtime.weights import CompactHostStore  # noqa: E402
+from flexible_llm_sharding_amd.utils.layer_format import layer_file, split_into_layers  # noqa: E402
+from flexible_llm_sharding_amd.utils.safetensors_io import load_file, save_file  # noqa: E402
+from flexible_llm_sharding_amd.utils.synthetic import write_synthetic_checkpoint  # noqa: E402
+from flexible_llm_sharding_amd.utils.tokenizer import load_tokenizer  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T = int4.TAIL
+DTYPES = [torch.float16, torch.bfloat16, torch.float32]
+
+
+# ----------------------------------------------------------------- definition
+def test_known_answer():
+    """The layout, literally: q = -8..7 packs to 0x76543210, 0xFEDCBA98."""
+    q = torch.arange(-8, 8, dtype=torch.int8).reshape(1, 16)
+    p = int4.pack(q)
+    assert p.dtype == torch.int32 and [x & 0xFFFFFFFF for x in p[0].tolist()] == [0x76543210, 0xFEDCBA98]
+    assert torch.equal(int4.unpack(p), q)
+    # the same as a little-endian byte stream: element i in byte i // 2, even i in the low nibble
+    assert p.numpy().astype("<i4").tobytes() == bytes([0x10, 0x32, 0x54, 0x76, 0x98, 0xBA, 0xDC, 0xFE])
+    # (g must be a multiple of 32: two rows of 16 would not do, so one row of 32 = the pattern twice)
+    p32 = int4.pack(torch.cat([q, q], 1))
+    w = int4.dequantize(p32, torch.tensor([[0.5]], dtype=torch.float16), (1, 32))
+    assert w.dtype == torch.float16 and w[0, :16].tolist() == [-4.0 + 0.5 * i for i in range(16)]
+    assert w[0, 16:].tolist() == w[0, :16].tolist()
+    n = int4.dequantize(p32, torch.tensor([-1.0]), (1, 32))                 # [out] is [out, 1]
+    assert n[0, 8].item() == 0 and n.view(torch.int16)[0, 8].item() == -32768      # q = 0: -0
+    assert n[0, 0].item() == 8.0 and n[0, 15].item() == -7.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("g", [32, 128, 0])
+def test_dequantize_equals_oracle(g, dtype):
+    gen = torch.Generator().manual_seed(7 + g)
+    out, inn = 24, 384
+    gg = g or inn
+    nib = torch.randint(0, 16, (out * inn,), generator=gen, dtype=torch.int64).to(torch.uint8)
+    packed = ir.words_of(nib, out, inn)
+    assert torch.equal(int4.pack(int4.unpack(packed)), packed)
+    assert np.array_equal(int4.unpack(packed).numpy().reshape(-1), ir.ref_unpack(packed, out * inn))
+    for extreme in (False, True):
+        s = ir.scales(out, inn // gg, dtype, gen, extreme)
+        assert ir.same_bits(int4.dequantize(packed, s, (out, inn)), ir.ref_dequant(packed, s, (out, inn)))
+    if g == 0:
+        s = ir.scales(out, 1, dtype, gen, False)
+        assert ir.same_bits(int4.dequantize(packed, s.reshape(out), (out, inn)), ir.ref_dequant(packed, s, (out, inn)))
+    for bad in (torch.ones(out, 5), torch.ones(out + 1, 1), torch.ones(out, inn // 16)):
+        with pytest.raises(ValueError):
+            int4.dequantize(packed, bad, (out, inn))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("g", [32, 128, 0])
+def test_quantize_error_bound(g, dtype):
+    """|w - w16| <= s / 2 + ulp16(w16) / 2, derived: w / s is rounded to the nearest integer, an error
+    of at most s / 2 in w; the clamp to 7 costs at most amax - 7 s <= 7 (s' - s) <= 7 * 2^-9 s' < s / 2
+    (s' the unrounded amax / 7, 2^-9 the largest relative rounding error of the three scale dtypes);
+    and the product q s is rounded once more, to fp16: half an ulp of the result."""
+    gen = torch.Generator().manual_seed(11)
+    out, inn = 16, 256
+    gg = g or inn
+    w = (torch.randn(out, inn, generator=gen) * 0.05).to(torch.float16)
+    w[3, :gg] = 0                                   # an all-zero group: scale 1, every q = 0
+    w[5, gg // 2] = 65504.0                         # a group holding a single 65504
+    packed, s = int4.quantize(w, g, dtype)
+    assert packed.shape == (out, inn // 8) and s.shape == (out, inn // gg) and s.dtype == dtype
+    assert float(s[3, 0]) == 1.0 and torch.isfinite(s.float()).all() and (s.float() > 0).all()
+    w16 = int4.dequantize(packed, s, (out, inn))
+    assert not w16[3, :gg].any()
+    full = s.to(torch.float64).repeat_interleave(gg, 1)
+    err = (w.to(torch.float64) - w16.to(torch.float64)).abs()
+    assert torch.isfinite(w16).all()
+    assert (err <= full / 2 + ir.ulp16(w16) / 2).all()
+    q = int4.unpack(packed)
+    assert int(q.min()) >= -8 and int(q.max()) <= 7 and int(q[5, gg // 2]) == 7
+    with pytest.raises(ValueError):
+        int4.quantize(w, 48, dtype)                 # no multiple of 32
+    with pytest.raises(ValueError):
+        int4.quantize(w[:, :160], 64, dtype)        # does not divide the row
+
+
+def test_quantize_state_dict_names():
+    from flexible_llm_sharding_amd.utils.synthetic import synthetic_layer_state_dict
+    cfg = preset("tiny")
+    sd = synthetic_layer_state_dict(cfg, "model.layers.0")
+    q = int4.quantize_state_dict(sd, 128, torch.bfloat16)
+    W = "model.layers.0.self_attn.q_proj.weight"
+    assert W not in q and q[W + "_packed"].dtype == torch.int32 and q[W + "_scale"].dtype == torch.bfloat16
+    assert q[W + "_shape"].dtype == torch.int64 and q[W + "_shape"].tolist() == list(sd[W].shape)
+    assert sum(k.endswith("_packed") for k in q) == 7
+    assert all(k in q for k in sd if "layernorm" in k)
+    again = int4.quantize_state_dict(q, 128, torch.bfloat16)          # already INT4: passes through
+    assert list(again) == list(q) and all(torch.equal(again[k], q[k]) for k in q)
+    for other in ("model.embed_tokens", "lm_head", "model.norm"):
+        o = synthetic_layer_state_dict(cfg, other)
+        assert list(int4.quantize_state_dict(o)) == list(o)
+    twin = int4.dequantize_state_dict(q)
+    assert list(sorted(twin)) == list(sorted(sd)) and twin[W].dtype == torch.float16
+
+
+# ------------------------------------------------------------ layout, schedule
+def _check_layout(n, g, es):
+    lay = int4.region_layout(n, g, es)
+    sched = int4.schedule(n, g, es)
+    assert sched == [(s.a, s.b) for s in lay]
+    # launches are contiguous and cover [0, n); every bound is a multiple of 32
+    assert sched[0][0] == 0 and sched[-1][1] == n
+    assert all(x[1] == y[0] for x, y in zip(sched, sched[1:]))
+    assert all(a % 32 == 0 and b % 32 == 0 and a < b for a, b in sched)
+    assert sched[-1][1] - sched[-1][0] <= T                          # the tail fits one block
+    top, groups = 2 * n, n // g
+    first = lay[0].scale_off
+    assert first >= 0
+    for j, s in enumerate(lay):
+        pb, sb = (s.b - s.a) // 2, s.n_groups * es
+        assert s.packed_off % 16 == 0 and s.scale_off % 16 == 0
+        # scales below nibbles, nibbles below the next segment; all inside the region
+        assert 0 <= s.scale_off and s.scale_off + sb <= s.packed_off and s.packed_off - (s.scale_off + sb) < 16
+        nxt = lay[j + 1].scale_off if j + 1 < len(lay) else top
+        assert s.packed_off + pb == nxt
+        assert (s.first_group, s.n_groups) == (s.a // g, s.b // g - s.a // g)
+        if j + 1 < len(lay):
+            # the no-overlap rule: a launch that is not the tail writes [2a, 2b) below everything unread
+            assert 2 * s.b <= s.scale_off
+    assert sum(s.n_groups for s in lay) == groups
+    assert int4.landing_span(n, g, es) == (first, top - first)
+    return lay
+
+
+@pytest.mark.parametrize("es", [2, 4])
+@pytest.mark.parametrize("g", [32, 128])
+def test_schedule_invariants(g, es):
+    for n in range(g, 4 * T + 1, 32):
+        if n % g == 0:
+            _check_layout(n, g, es)
+    for n in range(32, 4 * T + 1, 32):                                # every n = 32 k: per channel, g = n
+        _check_layout(n, n, es)
+    _check_layout(128 * 256, g, es)
+    big = _check_layout(8192 * 28672, g, es)
+    assert len(big) < 17                                              # fls_dequant_fp8's chain for this tensor
+    assert len(int4.schedule(T, g, es)) == 1 and len(int4.schedule(T + g, g, es)) == 2
+    # geometric: each launch leaves at most 0.32 of what was left (1/4 + es / 2g, plus alignment)
+    left = [8192 * 28672 - b for _, b in int4.schedule(8192 * 28672, g, es)]
+    assert all(y <= 0.32 * x + T for x, y in zip(left[1:], left[2:]))
+    for bad in ((64, 48, 2), (96, 64, 2), (64, 32, 3), (64, 0, 2)):
+        with pytest.raises(ValueError):
+            int4.region_layout(*bad)
+    assert int4.region_layout(0, 32, 2) == () and int4.schedule(0, 32, 2) == []
+
+
+def test_native_host_code_mirrors_the_schedule():
+    """The host code of fls_dequant_int4 computes region_layout() segment for segment (no GPU needed:
+    these entry points launch nothing)."""
+    import ctypes
+    from flexible_llm_sharding_amd import _native
+    k = _native.kernels()                               # (a library that is missing or does not load fails the test)
+    assert k.fls_dequant_int4_tail() == T
+    out = (ctypes.c_uint64 * 6)()
+    for g, es in ((32, 2), (32, 4), (128, 2), (128, 4), (2048, 4)):
+        ns = [n for n in range(g, 5 * T + 1, g)][::7] + [T - g, T, T + g, 2 * T + g, 5 * T - g, 1024 * 2048,
+                                                         8192 * 8192, 8192 * 28672]
+        for n in ns:
+            lay = int4.region_layout(n, g, es)
+            assert k.fls_dequant_int4_launches(n, g, es) == len(lay)
+            for j, s in enumerate(lay):
+                assert k.fls_dequant_int4_segment(n, g, es, j, ctypes.addressof(out)) == 0
+                assert tuple(out) == tuple(s), (n, g, es, j)
+            assert k.fls_dequant_int4_segment(n, g, es, len(lay), ctypes.addressof(out)) != 0
+    assert k.fls_dequant_int4_launches(96, 64, 2) < 0 and k.fls_dequant_int4_launches(64, 48, 2) < 0
+    assert k.fls_dequant_int4_launches(0, 32, 2) == 0
+
+
+def _emulate(region: np.ndarray, n: int, g: int, dtype) -> np.ndarray:
+    """Run the schedule launch by launch on the byte buffer: read ALL of a launch's sources (its
+    nibbles from its own segment; each scale from the segment that holds its group), then write ALL
+    of its outputs.  A write over a byte some later launch still needs shows as a wrong result."""
+    es = torch.empty((), dtype=dtype).element_size()
+    lay = int4.region_layout(n, g, es)
+    where = np.zeros(n // g, dtype=np.int64)                           # byte offset of every group's scale
+    for s in lay:
+        where[s.first_group:s.first_group + s.n_groups] = s.scale_off + np.arange(s.n_groups) * es
+    for s in lay:
+        nib = region[s.packed_off:s.packed_off + (s.b - s.a) // 2].copy()
+        ks = np.arange(s.a // g, (s.b - 1) // g + 1)
+        raw = region[where[ks][:, None] + np.arange(es)].reshape(-1).copy()
+        sc = torch.from_numpy(raw).view(dtype).to(torch.float32).numpy()
+        i = np.arange(s.a, s.b)
+        q = np.where(i % 2 == 0, nib[(i - s.a) // 2] & 15, nib[(i - s.a) // 2] >> 4).astype(np.int32) - 8
+        with np.errstate(over="ignore", invalid="ignore"):
+            w = (q.astype(np.float32) * sc[i // g - ks[0]]).astype(np.float16)
+        region[2 * s.a:2 * s.b] = np.frombuffer(w.tobytes(), dtype=np.uint8)
+    return region
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("g", [32, 128, 0])
+def test_in_place_emulation(g, dtype):
+    gen = torch.Generator().manual_seed(23 + g)
+    es = torch.empty((), dtype=dtype).element_size()
+    for rows, cols in ir.kernel_shapes(g, T) + [(64, 2048)]:             # (the kernel-test counts, and one more)
+        n, gg = rows * cols, g or cols
+        nib = torch.randint(0, 16, (n,), generator=gen, dtype=torch.int64).to(torch.uint8)
+        packed = ir.words_of(nib, rows, cols)
+        s = ir.scales(rows, cols // gg, dtype, gen, False)
+        region = torch.full((2 * n,), 0x5A, dtype=torch.uint8)           # stale bytes of the last occupant
+        int4.land(region, packed.view(torch.uint8).reshape(-1), s.reshape(-1).view(torch.uint8), n, gg, es)
+        base, span = int4.landing_span(n, gg, es)
+        assert (region[:base] == 0x5A).all()
+        got = torch.from_numpy(_emulate(region.numpy().copy(), n, gg, dtype)).view(torch.float16).reshape(rows, cols)
+        assert ir.same_bits(got, int4.dequantize(packed, s, (rows, cols))), (rows, cols)
+        # the torch backend expands the same landed bytes
+        from flexible_llm_sharding_amd.ops import get_ops
+        get_ops(torch.device("cpu")).dequant_int4(region, n, gg, dtype)
+        assert ir.same_bits(region.view(torch.float16).reshape(rows, cols), got)
+
+
+# ------------------------------------------------------------------------ plan
+@pytest.fixture(scope="module")
+def pairs(tmp_path_factory):
+    root = tmp_path_factory.mktemp("int4_pairs")
+    cache = {}
+
+    def get(name, group, scale_dtype=torch.float16):
+        key = (name, group, scale_dtype)
+        if key not in cache:
+            cache[key] = ir.make_pair(root, name, group, scale_dtype)
+        return cache[key]
+    return get
+
+
+def test_layer_plan_of_int4_layer(pairs):
+    cfg, q, twin = pairs("tiny", 128)
+    lname = "model.layers.1"
+    plan = LayerPlan(cfg, lname, layer_file(q, lname))
+    sd = load_file(layer_file(q, lname))
+    assert plan.int4_tensors == 7 == sum(k.endswith("_packed") for k in sd) and plan.fp8_tensors == 0
+    assert plan.file_bytes == ir.file_tensor_bytes(q, lname)
+    pls = {p.hf_name: p for p in placements(cfg, lname)}
+    for r in plan.runs:
+        if r.is_int4:
+            assert r.group == 128 and r.scale_dtype == torch.float16 and r.numel == pls[r.hf_name].numel
+            assert r.file_nbytes == r.numel // 2 + r.numel // 128 * 2
+            base, span = int4.landing_span(r.numel, 128, 2)
+            ps = r.int4_pieces()
+            assert sum(p[1] for p in ps) == r.file_nbytes and min(p[2] for p in ps) == base
+            assert all(base <= do and do + nb <= 2 * r.numel for _, nb, do in ps)
+    pieces = plan.pieces()
+    assert sum(p[1] for p in pieces) == plan.file_bytes
+    assert [p[0] for p in pieces] == sorted(p[0] for p in pieces)        # file order, as the streamer reads
+    r = next(r for r in plan.runs if r.is_int4)
+    for lo, hi in ((r.img_off + 2, r.img_off + 2 * r.numel), (0, r.img_off + r.numel), (r.img_off, r.img_off + 2 * r.numel - 2)):
+        with pytest.raises(ValueError, match="INT4"):
+            plan.pieces(lo, hi)
+    src = FileLayerSource(cfg, q)
+    for n in cfg.layer_names():
+        got = torch.zeros(src.nbytes(n), dtype=torch.uint8)
+        src.read_into(n, got)
+        want = pack_layer(cfg, n, load_file(layer_file(twin, n)))
+        assert torch.equal(got, want), n
+        assert torch.equal(pack_layer(cfg, n, load_file(layer_file(q, n))), want), n
+    assert src.int4_tensors() == 14 and src.file_bytes() == sum(ir.file_tensor_bytes(q, n) for n in cfg.layer_names())
+    store = CompactHostStore(FileLayerSource(cfg, q), pinned=False)
+    a16 = lambda x: (x + 15) // 16 * 16                              # noqa: E731
+    want = 0
+    for n in cfg.layer_names():
+        for r in store.plan(n).runs:
+            want += sum(a16(p[1]) for p in r.int4_pieces()) if r.is_int4 else a16(r.numel * min(r.src_es, 2))
+    assert store.total_bytes == want == store.pinned_bytes()
+
+
+# ---------------------------------------------------------------------- engine
+def _scores(cfg, src, path, prompts, **kw):
+    r = ShardedRunner(cfg, src, "cpu", load_tokenizer(path), **kw)
+    out = r(prompts)
+    r.close()
+    return out
+
+
+@pytest.mark.parametrize("name,group,scale_dtype", [("tiny", 128, torch.float16), ("tiny-mixtral", 64, torch.bfloat16)])
+def test_engine_int4_bitwise_equals_twin_cpu(pairs, name, group, scale_dtype):
+    cfg, q, twin = pairs(name, group, scale_dtype)
+    prompts = ir.prompts_for(cfg)
+    want = _scores(cfg, FileLayerSource(cfg, twin), twin, prompts)
+    for lnps in (1, 3):
+        got = _scores(cfg, FileLayerSource(cfg, q), q, prompts, layer_num_per_shard=lnps)
+        compact = _scores(cfg, CompactHostStore(FileLayerSource(cfg, q), pinned=False), q, prompts,
+                          layer_num_per_shard=lnps)
+        for w, a, b in zip(want, got, compact):
+            assert w.dtype == np.float16
+            assert np.array_equal(w.view(np.uint16), a.view(np.uint16))
+            assert np.array_equal(w.view(np.uint16), b.view(np.uint16))
+    if name == "tiny":                         # (the quantisation is not a no-op)
+        orig = os.path.join(os.path.dirname(q), "orig")
+        write_synthetic_checkpoint(cfg, orig, seed=3, std=0.05)
+        o = _scores(cfg, FileLayerSource(cfg, orig), orig, prompts)
+        assert any(not np.array_equal(x, y) for x, y in zip(o, want))
+
+
+# --------------------------------------------------------- converter, main.py
+def _env():
+    return dict(os.environ, PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+
+
+def _main(args, cwd):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py")] + args, cwd=cwd, env=_env(),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r
+
+
+def _same(a, b) -> bool:
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return (isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape
+                and a.tobytes() == b.tobytes())
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and list(a) == list(b) and all(_same(a[k], b[k]) for k in a)
+    return a == b
+
+
+@pytest.fixture(scope="module")
+def cli_pair(tmp_path_factory):
+    """prepare_weights.py --synthetic tiny --quantize int4, its twin, prompts and the twin's output."""
+    d = tmp_path_factory.mktemp("int4_cli")
+    q, twin = str(d / "q"), str(d / "twin")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "prepare_weights.py"), "tiny", q, "--synthetic",
+                        "--quantize", "int4", "--int4_group", "64", "--int4_scale_dtype", "bfloat16", "--std", "0.05"],
+                       env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    int4.write_twin(q, twin)
+    cfg = preset("tiny")
+    pp = d / "prompts.pkl"
+    pickle.dump(ir.prompts_for(cfg, 4), open(pp, "wb"))
+    out = d / "twin.pkl"
+    _main(["--model_path", twin, "--prompt_pickle", str(pp), "--output_file", str(out), "--num_gen_token", "2",
+           "--metrics_json", str(d / "twin.json")], str(d))
+    return cfg, q, twin, pp, open(out, "rb").read(), d
+
+
+def test_converter_writes_the_four_tensor_form(cli_pair, tmp_path):
+    cfg, q, twin, pp, _, d = cli_pair
+    sd = load_file(layer_file(q, "model.layers.0"))
+    W = "model.layers.0.mlp.down_proj.weight"
+    assert W not in sd and sd[W + "_packed"].dtype == torch.int32 and tuple(sd[W + "_packed"].shape) == (256, 512 // 8)
+    assert sd[W + "_scale"].dtype == torch.bfloat16 and tuple(sd[W + "_scale"].shape) == (256, 512 // 64)
+    assert sd[W + "_shape"].dtype == torch.int64 and sd[W + "_shape"].tolist() == [256, 512]
+    assert "model.layers.0.input_layernorm.weight" in sd
+    assert all(v.dtype == torch.float16 for v in load_file(layer_file(q, "model.embed_tokens")).values())
+    tw = load_file(layer_file(twin, "model.layers.0"))
+    assert not any(int4.is_companion_name(k) for k in tw) and tw[W].dtype == torch.float16
+    # an already-INT4 HF directory converts unchanged, companions included
+    hf, out = str(tmp_path / "hf"), str(tmp_path / "layers")
+    os.makedirs(hf)
+    full = {}
+    for n in cfg.layer_names():
+        full.update(load_file(layer_file(q, n)))
+    save_file(full, os.path.join(hf, "model.safetensors"))
+    for fn in os.listdir(q):
+        if not fn.endswith(".safetensors"):
+            import shutil
+            shutil.copy(os.path.join(q, fn), os.path.join(hf, fn))
+    split_into_layers(hf, out, verbose=False)
+    for n in cfg.layer_names():
+        a, b = load_file(layer_file(q, n)), load_file(layer_file(out, n))
+        assert sorted(a) == sorted(b) and all(a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]) for k in a), n
+    # and --quantize int4 of an INT4 directory leaves it as it is
+    out2 = str(tmp_path / "layers2")
+    split_into_layers(hf, out2, verbose=False, quantize="int4")
+    b = load_file(layer_file(out2, "model.layers.1"))
+    a = load_file(layer_file(q, "model.layers.1"))
+    assert sorted(a) == sorted(b) and all(torch.equal(a[k], b[k]) for k in a)
+
+
+def test_main_int4_equals_twin(cli_pair):
+    cfg, q, twin, pp, want, d = cli_pair
+    for tag, extra in (("host", ["--weight_cache", "host"]), ("stream", ["--weight_cache", "stream"])):
+        out = d / f"{tag}.pkl"
+        _main(["--model_path", q, "--prompt_pickle", str(pp), "--output_file", str(out), "--num_gen_token", "2",
+               "--metrics_json", str(d / f"{tag}.json")] + extra, str(d))
+        assert open(out, "rb").read() == want, tag
+        m = json.load(open(d / f"{tag}.json"))
+        assert m["int4_tensors"] == 14 and m["fp8_tensors"] == 0
+        assert m["weight_file_bytes"] == sum(ir.file_tensor_bytes(q, n) for n in cfg.layer_names())
+    m = json.load(open(d / "host.json"))
+    assert m["weight_file_bytes"] <= m["weight_pinned_bytes"] < m["weight_file_bytes"] + 16 * 200
+    mt = json.load(open(d / "twin.json"))
+    assert mt["int4_tensors"] == 0 and mt["weight_file_bytes"] > m["weight_file_bytes"]
+
+
+def test_gloo_data_parallel_unsharded_equals_twin(cli_pair, tmp_path):
+    """Two gloo ranks, --data_parallel with --dp_weight_shard false: the output of the same run on
+    the twin (a rank's slice of the prompts batches differently from the one-rank run)."""
+    cfg, q, twin, pp, _, d = cli_pair
+    outs = {}
+    for tag, path in (("int4", q), ("twin", twin)):
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        out = tmp_path / f"dp_{tag}.pkl"
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
+               "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "main.py"), "--model_path", path,
+               "--prompt_pickle", str(pp), "--output_file", str(out), "--num_gen_token", "2", "--num_gpus", "0",
+               "--data_parallel", "--dp_weight_shard", "false"]
+        r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs[tag] = pickle.load(open(out, "rb"))
+    assert len(outs["twin"]) == 4 and _same(outs["int4"], outs["twin"])
+
+
+# -------------------------------------------------------------------- refusals
+Q = "model.layers.0.self_attn.q_proj.weight"
+
+
+def _layer_with(tmp_path, cfg, edit):
+    d = str(tmp_path / "m")
+    write_synthetic_checkpoint(cfg, d, seed=1, std=0.05, quantize="int4")
+    p = layer_file(d, "model.layers.0")
+    sd = load_file(p)
+    edit(sd)
+    save_file(sd, p)
+    return d, p
+
+
+@pytest.mark.parametrize("case", ["both_forms", "zero_point", "g_idx", "packed_dtype", "packed_shape", "eight_bit", "no_shape",
+                                  "wrong_shape", "no_scale", "scale_dtype", "scale_shape", "group_48"])
+def test_refused_int4_tensors(tmp_path, case):
+    cfg = preset("tiny")
+
+    def edit(sd):
+        out, inn = sd[Q + "_shape"].tolist()
+        if case == "zero_point":
+            sd[Q + "_zero_point"] = torch.zeros(out, inn // 128, dtype=torch.int32)
+        elif case == "g_idx":
+            sd[Q + "_g_idx"] = torch.zeros(inn, dtype=torch.int32)
+        elif case == "packed_dtype":
+            sd[Q + "_packed"] = sd[Q + "_packed"].to(torch.int64)
+        elif case == "packed_shape":
+            sd[Q + "_packed"] = sd[Q + "_packed"][:, :-1].contiguous()
+        elif case == "eight_bit":
+            sd[Q + "_packed"] = torch.zeros(out, inn // 4, dtype=torch.int32)
+        elif case == "both_forms":
+            sd[Q] = torch.zeros(out, inn, dtype=torch.float16)
+        elif case == "no_shape":
+            del sd[Q + "_shape"]
+        elif case == "wrong_shape":
+            sd[Q + "_shape"] = torch.tensor([inn, out + 1], dtype=torch.int64)
+        elif case == "no_scale":
+            del sd[Q + "_scale"]
+        elif case == "scale_dtype":
+            sd[Q + "_scale"] = torch.ones(out, inn // 128, dtype=torch.int32)
+        elif case == "scale_shape":
+            sd[Q + "_scale"] = torch.ones(out + 1, 2, dtype=torch.float16)
+        else:
+            sd[Q + "_scale"] = torch.ones(out, inn // 16, dtype=torch.float16)     # g = 16: no multiple of 32
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(TypeError, match="q_proj.weight"):
+        LayerPlan(cfg, "model.layers.0", p)
+    with pytest.raises(TypeError, match="q_proj.weight"):
+        pack_layer(cfg, "model.layers.0", load_file(p))
+
+
+def test_refused_non_2d_placement(tmp_path):
+    """A norm weight (1-D placement) stored as INT4 words is refused by name."""
+    cfg = preset("tiny")
+    N = "model.layers.0.input_layernorm.weight"
+
+    def edit(sd):
+        del sd[N]
+        sd[N + "_packed"] = torch.zeros(1, 256 // 8, dtype=torch.int32)
+        sd[N + "_scale"] = torch.ones(1, 1, dtype=torch.float16)
+        sd[N + "_shape"] = torch.tensor([1, 256], dtype=torch.int64)
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(TypeError, match="input_layernorm.weight"):
+        LayerPlan(cfg, "model.layers.0", p)
+
+
+def test_unlisted_family_accepts_the_companions(pairs):
+    import dataclasses
+    cfg, q, twin = pairs("tiny", 128)
+    other = dataclasses.replace(cfg, model_type="some_llama_like") if dataclasses.is_dataclass(cfg) else None
+    if other is None:
+        other = preset("tiny")
+        other.model_type = "some_llama_like"
+    assert LayerPlan(other, "model.layers.0", layer_file(q, "model.layers.0")).int4_tensors == 7
+    sd = load_file(layer_file(q, "model.layers.0"))
+    sd["model.layers.0.self_attn.q_norm.weight_packed"] = torch.zeros(1, 4, dtype=torch.int32)   # (no such weight)
+    with pytest.raises(NotImplementedError):
+        pack_layer(other, "model.layers.0", sd)
+
+
+def test_refused_dp_weight_shard(pairs):
+    from flexible_llm_sharding_amd.api import build_runner, check_fp8_dp_shard
+    from flexible_llm_sharding_amd.utils.cli import parse_args
+    cfg, q, twin = pairs("tiny", 128)
+    with pytest.raises(ValueError, match="--dp_weight_shard.*INT4"):
+        check_fp8_dp_shard(types.SimpleNamespace(model_path=q, synthetic=None, score_mode="next_token"), cfg)
+    check_fp8_dp_shard(types.SimpleNamespace(model_path=twin, synthetic=None, score_mode="next_token"), cfg)
+    args = parse_args(["--model_path", q, "--prompt_pickle", "p.pkl", "--output_file", "o.pkl", "--data_parallel",
+                       "--dp_weight_shard", "true"])
+    comm = types.SimpleNamespace(world=2, rank=0, active=True)
+    with pytest.raises(ValueError, match="--dp_weight_shard"):
+        build_runner(args, cfg, "cpu", comm, load_tokenizer(q))
+    store = CompactHostStore(FileLayerSource(cfg, q), pinned=False)
+    assert store.norms_folded is False and store.host_buffer("model.layers.0") is None
+
+
+def test_resolve_weight_cache_sizes_int4_by_file_bytes(pairs):
+    from flexible_llm_sharding_amd.api import build_source, resolve_weight_cache
+    from flexible_llm_sharding_amd.models.layout import layer_kind, layer_layout
+    from flexible_llm_sharding_amd.parallel.comm import Comm
+    cfg, q, twin = pairs("tiny", 128)
+    names = cfg.layer_names()
+    comm = Comm(0, 1)
+    src, tsrc = FileLayerSource(cfg, q), FileLayerSource(cfg, twin)
+    image = sum(layer_layout(cfg, layer_kind(n)).nbytes for n in names)
+    files = src.file_bytes()
+    assert files < image
+    between = (files + image) / 2 / 1e9
+
+    def args(mode, gb, path=q):
+        return types.SimpleNamespace(weight_cache=mode, host_mem_gb=gb, synthetic=None, model_path=path,
+                                     layer_num_per_shard=1, data_parallel=False, verbose=False)
+    assert resolve_weight_cache(args("auto", between), cfg, comm, names, sliced=False, source=src) == "host"
+    assert resolve_weight_cache(args("auto", between), cfg, comm, names, sliced=False, source=tsrc) == "stream"
+    st = build_source(args("host", between), cfg, comm, torch.device("cpu"))
+    assert isinstance(st, CompactHostStore) and st.files.int4_tensors() == 14
+    assert isinstance(build_source(args("stream", between), cfg, comm, torch.device("cpu")), FileLayerSource)

@@ -1,0 +1,243 @@
+"""Weight-only INT4 (W4A16, group scales) checkpoints on an MI355X: ``fls_dequant_int4`` equals the
+host definition (int4.dequantize) in every bit, in place, with no byte written outside the tensor's
+region; and a run on an INT4 checkpoint — streamed, pinned compact, resident, through the sub-layer
+piece pool, and generating through decode graphs — equals the same run on its fp16 twin in every bit
+while moving a quarter of the weight bytes."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import int4_ref as ir  # noqa: E402
+
+from flexible_llm_sharding_amd import int4  # noqa: E402
+
+HAS_GPU = torch.cuda.is_available()
+gpu = pytest.mark.gpu
+needs_gpu = pytest.mark.skipif(not HAS_GPU, reason="needs an MI355X")
+DEV = torch.device("cuda", 0)
+CANARY = 64
+DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}
+
+
+def _tail() -> int:
+    from flexible_llm_sharding_amd import _native
+    return int(_native.kernels().fls_dequant_int4_tail())
+
+
+def _run_kernel(ops, packed: torch.Tensor, scale: torch.Tensor, rows: int, cols: int, g: int, base_off: int):
+    """The kernel in place on a region at ``base_off`` bytes past a 256-byte aligned address, between
+    two 64-byte canaries, stale 0x5A below the landed bytes.  Returns (fp16 result, canaries intact)."""
+    n, es = rows * cols, scale.element_size()
+    host = torch.full((2 * n,), 0x5A, dtype=torch.uint8)
+    int4.land(host, packed.view(torch.uint8).reshape(-1), scale.reshape(-1).view(torch.uint8), n, g, es)
+    assert (host[:int4.landing_span(n, g, es)[0]] == 0x5A).all()
+    buf = torch.full((512 + base_off + 2 * n + CANARY,), 0xA5, dtype=torch.uint8, device=DEV)
+    start = (-buf.data_ptr()) % 256 + 256 + base_off             # (at least 256 >= CANARY bytes in front)
+    assert (buf.data_ptr() + start - base_off) % 256 == 0
+    region = buf[start:start + 2 * n]
+    region.copy_(host.to(DEV))
+    ops.dequant_int4(region, n, g, scale.dtype)
+    torch.cuda.synchronize()
+    back = buf.cpu()
+    ok = bool((back[:start] == 0xA5).all()) and bool((back[start + 2 * n:] == 0xA5).all())
+    return back[start:start + 2 * n].clone().view(torch.float16).reshape(rows, cols), ok
+
+
+@gpu
+@needs_gpu
+@pytest.mark.parametrize("base_off", [0, 2, 6])
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("g", [32, 128, 0])                      # (0: per channel, g = cols)
+def test_dequant_int4_equals_host(g, dt, base_off):
+    from flexible_llm_sharding_amd import _native
+    from flexible_llm_sharding_amd.ops import get_ops
+    ops, k, dtype = get_ops(DEV), _native.kernels(), DTYPES[dt]
+    es = torch.empty((), dtype=dtype).element_size()
+    gen = torch.Generator().manual_seed(1000 * g + 10 * es + base_off)
+    T = _tail()
+    assert T == int4.TAIL and T % 256 == 0
+    shapes = ir.kernel_shapes(g, T)
+    gq = g or 256
+    assert {r * c for r, c in shapes} >= {gq, T - gq, T, T + gq, 2 * T + gq, 5 * T - gq, 1024 * 2048}
+    for rows, cols in shapes:
+        n, gg = rows * cols, g or cols
+        assert k.fls_dequant_int4_launches(n, gg, es) == len(int4.schedule(n, gg, es))
+        for mode, extreme in (("lanes", False), ("lanes", True), ("random", False)):
+            nib = ir.lanes(n) if mode == "lanes" else torch.randint(0, 16, (n,), generator=gen, dtype=torch.int64).to(torch.uint8)
+            packed = ir.words_of(nib, rows, cols)
+            scale = ir.scales(rows, cols // gg, dtype, gen, extreme)
+            want = int4.dequantize(packed, scale, (rows, cols))
+            got, intact = _run_kernel(ops, packed, scale, rows, cols, gg, base_off)
+            assert intact, (rows, cols, mode, "canary overwritten")
+            assert ir.same_bits(got, want), (rows, cols, mode, extreme)
+            if n in (2 * T + gq, 5 * T - gq) and mode == "random":
+                again, intact = _run_kernel(ops, packed, scale, rows, cols, gg, base_off)
+                assert intact and torch.equal(again.view(torch.int16), got.view(torch.int16))
+    assert k.fls_dequant_int4_launches(T, 32, es) == 1 and k.fls_dequant_int4_launches(T + 32, 32, es) == 2
+    assert k.fls_dequant_int4_launches(8192 * 28672, gq, es) == len(int4.schedule(8192 * 28672, gq, es)) < 17
+    assert k.fls_dequant_int4(None, 0, 32, 0, None) == 0
+
+
+@gpu
+@needs_gpu
+def test_dequant_int4_refusals():
+    from flexible_llm_sharding_amd import _native
+    from flexible_llm_sharding_amd.ops import get_ops
+    ops, k = get_ops(DEV), _native.kernels()
+    region = torch.zeros(2 * 128, dtype=torch.uint8, device=DEV)
+    p = region.data_ptr()
+    assert k.fls_dequant_int4(None, 128, 32, 0, None) != 0                  # a null pointer
+    assert k.fls_dequant_int4(p + 1, 64, 32, 0, None) != 0                  # an odd region address
+    assert k.fls_dequant_int4(p, 96, 48, 0, None) != 0                      # group % 32
+    assert k.fls_dequant_int4(p, 128, 0, 0, None) != 0
+    assert k.fls_dequant_int4(p, 96, 64, 0, None) != 0                      # n % group
+    assert k.fls_dequant_int4(p, 128, 32, 3, None) != 0                     # an unknown scale dtype
+    assert k.fls_dequant_int4(p, 128, 32, -1, None) != 0
+    assert k.fls_dequant_int4_launches(96, 64, 2) < 0 and k.fls_dequant_int4_launches(64, 32, 3) < 0
+    with pytest.raises(ValueError):
+        ops.dequant_int4(region, 96, 32, torch.float16)                     # region is not 2 bytes per weight
+    with pytest.raises(ValueError):
+        ops.dequant_int4(region, 128, 48, torch.float16)
+    with pytest.raises(TypeError):
+        ops.dequant_int4(region, 128, 32, torch.int32)
+    torch.cuda.synchronize()
+    assert not region.any()
+
+
+# ---------------------------------------------------------------------- engine
+PRESETS = {"tiny": (128, torch.float16), "tiny-qwen2": (32, torch.bfloat16), "tiny-phi3": (0, torch.float32),
+           "tiny-mixtral": (64, torch.float16)}
+_PAIRS = {}
+PLAN_KEYS = ("token_budget", "mlp_chunk", "attn_rows", "qkv_chunk")
+
+
+@pytest.fixture(scope="module")
+def pair(tmp_path_factory):
+    """(cfg, int4 dir, twin dir, tokenizer, prompts, the twin's scores per lnps) per preset, built once."""
+    root = tmp_path_factory.mktemp("int4_gpu")
+
+    def get(name):
+        if name not in _PAIRS:
+            from flexible_llm_sharding_amd.utils.tokenizer import load_tokenizer
+            cfg, q, twin = ir.make_pair(root, name, *PRESETS[name])
+            _PAIRS[name] = (cfg, q, twin, load_tokenizer(q), ir.prompts_for(cfg, 4), {})
+        return _PAIRS[name]
+    return get
+
+
+def _twin_scores(p, lnps, **kw):
+    """The twin's scores (and memory plan) through the ordinary FileLayerSource, once per (lnps, cap)."""
+    from flexible_llm_sharding_amd.engine import ShardedRunner
+    from flexible_llm_sharding_amd.runtime.stream import FileLayerSource
+    cfg, q, twin, tok, prompts, cache = p
+    key = (lnps, tuple(sorted(kw.items())))
+    if key not in cache:
+        r = ShardedRunner(cfg, FileLayerSource(cfg, twin), DEV, tok, layer_num_per_shard=lnps, **kw)
+        out = r(prompts)
+        cache[key] = (out, dict(r.vram_plan) if r.vram_plan else None)
+        r.close()
+    return cache[key]
+
+
+def _source(mode, cfg, q):
+    from flexible_llm_sharding_amd.runtime.stream import FileLayerSource
+    from flexible_llm_sharding_amd.runtime.weights import CompactHostStore
+    if mode == "compact":
+        return CompactHostStore(FileLayerSource(cfg, q))
+    return FileLayerSource(cfg, q, chunk_mb=1, n_chunks=2, direct=mode == "stream_direct")
+
+
+@gpu
+@needs_gpu
+@pytest.mark.parametrize("mode,lnps", [(m, l) for m in ("stream", "stream_direct", "compact", "resident")
+                                       for l in (1, 3)] + [("piece_pool", 1)])   # (the pool: one layer per shard)
+@pytest.mark.parametrize("name", list(PRESETS))
+def test_engine_int4_bitwise_equals_twin(pair, name, mode, lnps):
+    from flexible_llm_sharding_amd.engine import ShardedRunner
+    from flexible_llm_sharding_amd.runtime.prefetch import PiecePoolPrefetcher
+    p = pair(name)
+    cfg, q, twin, tok, prompts, _ = p
+    kw = {"resident": True} if mode == "resident" else {"max_vram_gb": 40} if mode == "piece_pool" else {}
+    # (a capped run plans its own chunks: its twin runs under the same cap)
+    want, want_plan = _twin_scores(p, lnps, **({"max_vram_gb": 40} if mode == "piece_pool" else {}))
+    src = _source("compact" if mode == "piece_pool" and name != "tiny" else mode, cfg, q)
+    r = ShardedRunner(cfg, src, DEV, tok, layer_num_per_shard=lnps, **kw)
+    if mode == "piece_pool":
+        assert isinstance(r.prefetcher, PiecePoolPrefetcher)
+    first = r(prompts)
+    second = r(prompts)                      # slot rotation, re-expansion into a reused slot
+    plan = dict(r.vram_plan) if r.vram_plan else None
+    r.close()
+    for w, a, b in zip(want, first, second):
+        assert a.dtype == np.float16 and np.array_equal(w.view(np.uint16), a.view(np.uint16))
+        assert np.array_equal(w.view(np.uint16), b.view(np.uint16))
+    if mode == "piece_pool":
+        # the scales travel with the weights: the plan of a capped run is the twin's, chunk for chunk
+        assert plan is not None and want_plan is not None
+        assert {k: plan[k] for k in PLAN_KEYS} == {k: want_plan[k] for k in PLAN_KEYS}
+    files = src if hasattr(src, "int4_tensors") else src.files
+    assert files.int4_tensors() > 0 and files.scale_arena_bytes() == 0
+
+
+@gpu
+@needs_gpu
+def test_generation_int4_bitwise(pair):
+    """num_gen_token = 3, resident weights, decode graphs: tokens and every step's scores equal the twin's."""
+    import topk_ref as tr
+    from flexible_llm_sharding_amd.runtime.stream import FileLayerSource
+    cfg, q, twin, tok, prompts, _ = pair("tiny")
+    runs = {}
+    for tag, path in (("int4", q), ("twin", twin)):
+        runs[tag] = tr.generate((cfg, tok, prompts, FileLayerSource(cfg, path)), DEV, num_gen=3)
+    a, b = runs["int4"], runs["twin"]
+    assert a.updated == b.updated and len(a.scores) == len(b.scores)
+    for x, y in zip(a.scores, b.scores):
+        assert x.shape[1] == 3 and np.array_equal(x.view(np.uint16), y.view(np.uint16))
+    for sa, sb in zip(a.tokens, b.tokens):
+        assert all(np.array_equal(u, v) for u, v in zip(sa, sb))
+    assert a.stats[-1].get("graph_replays", 0) >= 1
+
+
+@gpu
+@needs_gpu
+def test_int4_moves_a_quarter_of_the_bytes(pair):
+    from flexible_llm_sharding_amd.engine import ShardedRunner
+    from flexible_llm_sharding_amd.runtime.stream import FileLayerSource
+    from flexible_llm_sharding_amd.runtime.weights import CompactHostStore
+    cfg, q, twin, tok, prompts, _ = pair("tiny")
+    g, es = 128, 2
+    names, dec = cfg.layer_names(), ir.decoder_names(cfg)
+    src = FileLayerSource(cfg, q, chunk_mb=1, n_chunks=2)
+    files = sum(src.plan(n).file_bytes for n in names)
+    assert files == sum(ir.file_tensor_bytes(q, n) for n in names)
+    # (two slots: the engine then prefetches nothing of the next call, so one call is one pass)
+    r = ShardedRunner(cfg, src, DEV, tok, layer_num_per_shard=1, n_slots=2)
+    r(prompts)
+    torch.cuda.synchronize()
+    st = src.stats()
+    # one pass reads and copies exactly the files' tensor bytes
+    assert int(st["h2d_bytes"]) == files and src.read_bytes == files == int(st["read_bytes"])
+    r.close()
+    # decoder layers: at most 0.25 + es / 2g of the twin's bytes for the quantised weights, plus the norms
+    tsrc = FileLayerSource(cfg, twin)
+    for n in dec:
+        runs = src.plan(n).runs
+        quant = sum(2 * r_.numel for r_ in runs if r_.is_int4)
+        rest = sum(r_.file_nbytes for r_ in runs if not r_.is_int4)
+        assert quant > 0 and quant + rest == tsrc.plan(n).file_bytes
+        assert src.plan(n).file_bytes <= (0.25 + es / (2 * g)) * quant + rest
+    # the compact store pins every piece at a 16-byte aligned offset: sum of align16(bytes)
+    store = CompactHostStore(FileLayerSource(cfg, q))
+    a16 = lambda n: (n + 15) // 16 * 16                          # noqa: E731
+    assert store.COMPACT_ALIGN == 16
+    want = 0
+    for n in names:
+        for r_ in store.plan(n).runs:
+            want += sum(a16(p[1]) for p in r_.int4_pieces()) if r_.is_int4 else a16(r_.file_nbytes)
+    assert store.total_bytes == want
+    assert files <= store.total_bytes < files + 16 * sum(len(store.plan(n).pieces()) for n in names)
+    store.close()
