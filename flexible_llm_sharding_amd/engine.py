@@ -46,11 +46,11 @@ from .parallel.planner import ShardPlan, make_plan
 from .runtime import hostmem
 from .runtime.activations import ActivationStore, ActRing
 from .runtime.batch import Q_BLOCK, Q_BLOCK_MHA, PackedBatch, pack_prompts, split_microbatches
+from .runtime.outputs import CallResults, Outputs
 from .runtime.prefetch import ShardPrefetcher
 from .runtime.weights import LayerSource
 from .sampling import MAX_VOCAB
-from .sampling import draws as sample_draws
-from .topk import TOPK_DTYPE, check_k
+from .topk import check_k
 from .utils import trace
 from .utils.tokenizer import TokenizedPrompt, tokenize_prompts
 
@@ -98,63 +98,43 @@ class ShardedRunner:
         self.embed: Optional[EmbedParams] = None
         given = [f for f, v in (("--embed_pooling", embed_pooling), ("--embed_dim", embed_dim),
                                 ("--embed_normalize", embed_normalize)) if v is not None]
+        if given and score_mode != "embed":
+            raise ValueError(f"{given[0]} needs --score_mode embed")
+        # loglik and embed are one full pass each (every suffix token scored / pooled): the paths that
+        # replay, reuse or hand over parts of a pass are not wired for them, and they draw and rank
+        # no token
+        world = comm.world if comm is not None else 1
+        partial = [(hip_graphs, "--hip_graphs"), (prefix_kv_cache, "--prefix_kv_cache"),
+                   (suffix_kv_cache, "--suffix_kv_cache"), (resume_dir, "--resume_dir")]
+        tokens = [(sampling is not None, "--do_sample"), (score_top_k, "--score_top_k")]
+        mp = [(world > 1 and not data_parallel, "model parallel (several GPUs without --data_parallel)")]
+        for mode, on, msg in (
+                [("embed", on, f"--score_mode embed does not combine with {flag}") for on, flag in partial + tokens + mp]
+                + [("loglik", on, f"--score_mode loglik does not combine with {flag}") for on, flag in partial + mp]
+                + [("loglik", on, f"{flag} does not combine with --score_mode loglik") for on, flag in tokens]):
+            if on and score_mode == mode:
+                raise ValueError(msg)
         if score_mode == "embed":
-            world = comm.world if comm is not None else 1
-            for on, flag in ((hip_graphs, "--hip_graphs"), (prefix_kv_cache, "--prefix_kv_cache"),
-                             (suffix_kv_cache, "--suffix_kv_cache"), (resume_dir, "--resume_dir"),
-                             (sampling is not None, "--do_sample"), (score_top_k, "--score_top_k"),
-                             (world > 1 and not data_parallel,
-                              "model parallel (several GPUs without --data_parallel)")):
-                if on:
-                    raise ValueError(f"--score_mode embed does not combine with {flag}")
             self.embed = EmbedParams(embed_pooling or "last", int(embed_dim or 0),
                                      True if embed_normalize is None else bool(embed_normalize)
                                      ).resolved(cfg.hidden_size)
-        elif given:
-            raise ValueError(f"{given[0]} needs --score_mode embed")
         # every suffix row leaves the last decoder layer (loglik: each is scored; mean pooling: each
         # is pooled), so that layer runs unpruned and the final norm gathers the rows
         self._all_suffix_rows = self.loglik or (self.embed is not None and self.embed.pooling == "mean")
         # (mean pooling's other variant, kept for measurements — set_mean_variant: the last layer
         # pruned to the suffix rows through pack_prompts(score_rows=...); profiles/embed has both)
         self._mean_pruned = False
-        if self.loglik:
-            # continuation log-likelihood: every suffix token is scored in one full pass; the paths
-            # that replay, reuse or hand over parts of a pass are not wired for it
-            world = comm.world if comm is not None else 1
-            for on, flag in ((hip_graphs, "--hip_graphs"), (prefix_kv_cache, "--prefix_kv_cache"),
-                             (suffix_kv_cache, "--suffix_kv_cache"), (resume_dir, "--resume_dir"),
-                             (world > 1 and not data_parallel,
-                              "model parallel (several GPUs without --data_parallel)")):
-                if on:
-                    raise ValueError(f"--score_mode loglik does not combine with {flag}")
         # sampled generation (sampling.SamplingParams; None: greedy): every next token is drawn by
-        # _pick_rows from the row's fp16 probabilities, as a function of (row, seed, prompt index,
+        # Outputs.pick from the row's fp16 probabilities, as a function of (row, seed, prompt index,
         # suffix index, step) only
-        if sampling is not None and self.loglik:
-            raise ValueError("--do_sample does not combine with --score_mode loglik")
         if sampling is not None and cfg.vocab_size >= MAX_VOCAB:
             raise ValueError(f"--do_sample supports vocabularies below {MAX_VOCAB}, got {cfg.vocab_size}")
         self.sampling = sampling
         # compact scores (topk.py; 0: off): per scored row the K best (token id, probability) pairs
         # and the chosen token's probability leave the device instead of the [rows, V] scores
-        if score_top_k:
-            if self.loglik:
-                raise ValueError("--score_top_k does not combine with --score_mode loglik")
-            score_top_k = check_k(score_top_k, cfg.vocab_size)
-        self.score_top_k = int(score_top_k)
-        # last call's probability of each suffix's chosen token (score_top_k): fp16 [n_s, 1] per prompt
-        self.last_token_probs: List[Optional[np.ndarray]] = []
-        self.score_d2h_bytes = 0           # bytes of scores the last call copied to the host
-        # prompt-lookup drafts (run_tokenized(drafts=...)): the last such call's accepted draft tokens
-        # per prompt ([n_s] int64), and the rows it scored / kept
-        self.last_accept: List[Optional[np.ndarray]] = []
-        self.lookup_rows = self.lookup_kept = 0
+        self.score_top_k = int(check_k(score_top_k, cfg.vocab_size)) if score_top_k else 0
         self.sample_step = 0               # the generation step of the next call (api.generation_loop)
         self.prompt_base = 0               # index in the prompt file of the next call's first prompt
-        self._sample_table: Optional[torch.Tensor] = None
-        # last call's per-token log-probabilities (loglik): per prompt a list of n_s float32 arrays
-        self.last_token_logprobs: List[Optional[List[np.ndarray]]] = []
         self.sliding_window_mode = sliding_window_mode
         self.cfg = cfg
         self.src = source
@@ -324,10 +304,10 @@ class ShardedRunner:
         self._graphs = None
         self._decode_graphs = None
         self._spec: Optional[dict] = None     # an enqueued speculative generation step
-        self.last_tokens: List[Optional[np.ndarray]] = []   # last call's greedy (or sampled) token per suffix
-        if self.sampling is not None:
-            # the weight table, uploaded once (every weight is <= 2^30: the uint32 values as int32)
-            self._sample_table = torch.from_numpy(self.sampling.table().view(np.int32)).to(self.dev)
+        # everything between the last layer's result and the caller's arrays (runtime/outputs.py)
+        self.out = Outputs(score_mode, self.score_top_k, sampling, self.embed, self.ops, self.dev,
+                           self._get_store, self.d2h_stream)
+        self._publish(CallResults())
         if self.cuda and not self.hip_graphs:
             from .models.llama import Workspace
             self.ctx.ws = Workspace(self.dev, self.act_dtype)   # fixed scratch buffers (VRAM plan)
@@ -603,18 +583,15 @@ class ShardedRunner:
         [kept] arrays (each kept row's greedy token), ``last_accept`` the accepted counts.  Rejected
         rows never leave the device.  Such a call runs eagerly (no decode graph) and row-exact."""
         t_start = time.perf_counter()
+        res = CallResults.begin(tps, self.loglik)
         spec, self._spec = self._spec, None
         if spec is not None:
             if drafts is None and self._spec_matches(spec, tps):
-                return self._finish_spec(spec, tps, t_start)
+                return self._finish_spec(spec, tps, t_start, res)
             self._drop_spec(spec)
-        n = len(tps)
         score_rows = self._check_drafts(tps, drafts) if drafts is not None else None
-        self.lookup_rows = self.lookup_kept = 0
         if self.loglik:
             self._check_loglik(tps)
-            self._pair_lens = [[len(s) for s in tp.suffixes] for tp in tps]
-            self.last_token_logprobs = [None] * n
         pool = None
         if self.embed is not None:
             self._check_embed(tps)
@@ -657,15 +634,15 @@ class ShardedRunner:
         t_pack = time.perf_counter() - t_start
         if self.hip_graphs:
             with self._workspace():
-                return self._run_graphed(tps, batches, t_start)
+                return self._run_graphed(tps, batches, t_start, res)
         self.ctx.prefix_entry = entry
         try:
             with self._workspace(), self._row_exact(self.row_exact):
                 if (self._decode_graphable(batches, cached) and not entry.host      # (graphs: K/V in HBM)
                         and drafts is None):
-                    outputs = self._run_graphed(tps, batches, t_start, entry=entry)
+                    outputs = self._run_graphed(tps, batches, t_start, res, entry=entry)
                 else:
-                    outputs = self._run_batches(tps, batches, t_start)
+                    outputs = self._run_batches(tps, batches, t_start, res)
         except BaseException:
             if entry is not None and not cached:
                 self.prefix_cache.drop(entry)
@@ -765,11 +742,11 @@ class ShardedRunner:
     class _Pass:
         """Mutable state of one ``_run_batches`` call."""
 
-        def __init__(self, tps, batches, metas, store, items):
+        def __init__(self, tps, batches, metas, store, items, res):
             self.tps, self.batches, self.metas, self.store, self.items = tps, batches, metas, store, items
             self.pos = {it: i for i, it in enumerate(items)}
-            self.outputs: List[Optional[np.ndarray]] = [None] * len(tps)
-            self.out_pending = []      # (batch, host tensor, event, pool buffer)
+            self.res: CallResults = res
+            self.out_pending = []      # outputs.Pending of every finished micro-batch
             self.carry = {}            # micro-batch -> device activation kept across a shard boundary
             self.sends = []            # (tensor, work) of outputs in flight to another rank
             self.shard_ev: List = []   # end-of-shard events on the compute stream (host run-ahead bound)
@@ -787,7 +764,7 @@ class ShardedRunner:
             self.ring: Optional[ActRing] = None      # hidden-state slots (storage cpu / disk, local passes)
             self.landed = {}           # micro-batch -> (ring-slot state, H2D event) landed ahead of its use
 
-    def _run_batches(self, tps, batches, t_start: float) -> List[Optional[np.ndarray]]:
+    def _run_batches(self, tps, batches, t_start: float, res: CallResults) -> List[Optional[np.ndarray]]:
         metas = [b.device_tensors(self.dev) for b in batches]   # all uploads before any compute
         store = self._get_store()
         store.bytes_d2h = store.bytes_h2d = store.buffer_waits = 0
@@ -801,7 +778,7 @@ class ShardedRunner:
         # speculative one), not from the first acquire
         h2d0 = pf.bytes_h2d if self._h2d0 is None else self._h2d0
         self._h2d0 = None
-        px = self._Pass(tps, batches, metas, store, self.schedule(len(batches)))
+        px = self._Pass(tps, batches, metas, store, self.schedule(len(batches)), res)
         collective = getattr(pf, "collective", False)
         # the resume point first: ranks agree on it with a collective on the default group, which
         # every rank must reach before any weight gather (a rank without prompts included)
@@ -1010,7 +987,8 @@ class ShardedRunner:
             # stays on this rank (contiguous stages) leaves the slot first
             state = state.clone()
         if last == self.L - 1:
-            px.out_pending.append(self._start_output_copy(px.batches[b], state))
+            px.out_pending.append(self.out.start(px.batches[b], state, self.sample_step, self.d2h_stream,
+                                                 self.prompt_base))
         elif px.dst_rank != self.comm.rank:
             st = state.contiguous()
             w = self.comm.isend(st, px.dst_rank)
@@ -1078,14 +1056,7 @@ class ShardedRunner:
         if px.inbox is not None:
             px.inbox.end_call()
             rx_stats = {f"rx_{k}": float(v) for k, v in px.inbox.stats.items()}
-        self.last_tokens = [None] * len(px.tps)
-        self.last_token_probs = [None] * len(px.tps)
-        self.last_accept = [None] * len(px.tps)
-        self.score_d2h_bytes = 0
-        for batch, host, ev, pool_buf, am in px.out_pending:
-            self._collect(batch, host.numpy(), am, px.outputs)
-            if pool_buf is not None:
-                store.recycle_host(pool_buf)
+        self.out.collect(px.out_pending, px.res)
         store.clear()
         store.trim()                   # pinned pool follows this call's shapes
         wait_s = pf.take_wait_seconds()
@@ -1117,7 +1088,7 @@ class ShardedRunner:
             print(f"{self.dev} rank{self.comm.rank}: loaded {n_layers} layers in {wait_s:.2f}s "
                   f"(exposed weight wait); {len(self.my_shards)} shards, {len(batches)} micro-batches, "
                   f"{self.stats['tokens']:.0f} tokens in {wall:.2f}s")
-        return px.outputs
+        return self._publish(px.res)
 
     # model parallel: outputs waiting for their consumer before the host waits for the oldest
     SEND_WINDOW = 3
@@ -1220,7 +1191,7 @@ class ShardedRunner:
                     and all(b.work2 is not None for b in batches)
                     and (pf.resident or (getattr(pf, "all_kept_loaded", None) is not None and pf.all_kept_loaded())))
 
-    def _run_graphed(self, tps, batches, t_start: float, entry=None) -> List[Optional[np.ndarray]]:
+    def _run_graphed(self, tps, batches, t_start: float, res: CallResults, entry=None) -> List[Optional[np.ndarray]]:
         """Static-weights path: one graph replay per micro-batch (runtime/graphs.py): resident
         full forwards (``--hip_graphs``), or decode-like calls on the prefix / suffix K/V cache
         ``entry`` (exact shapes; the graph reads and writes the entry's per-layer K/V in place).
@@ -1245,75 +1216,27 @@ class ShardedRunner:
                 self._graphs = GraphedForward(self.dev, self._forward_all)
             graphs = self._graphs
             run = graphs.run
-        outputs: List[Optional[np.ndarray]] = [None] * len(tps)
         ws, self.ctx.ws = self.ctx.ws, None           # the graph's own memory pool, not the arena
         try:
-            pending, ams, flops = self._enqueue_graphed(batches, lambda b, i: run(b))
+            pending, flops = self._enqueue_graphed(batches, lambda b, i: run(b))
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(self.dev))
             if entry is not None and self.spec_steps > 0:
                 # the next generation step, enqueued behind this one (see _launch_spec)
-                self._spec = self._launch_spec(tps, entry, batches, ams)
+                self._spec = self._launch_spec(tps, entry, batches, pending)
         finally:
             self.ctx.ws = ws
         done.synchronize()                            # this step's scores (not the speculative one)
-        self._collect_graphed(pending, outputs, len(tps))
-        if self._spec is not None:
-            self._spec["prev_tokens"] = list(self.last_tokens)
-        wall = time.perf_counter() - t_start
-        self.stats = {
-            "wall_s": wall, "compute_launch_s": wall,
-            "tokens": float(sum(b.num_tokens for b in batches)),
-            "padded_tokens": float(sum(b.padded_tokens for b in batches)),
-            "decoder_flops": flops, "micro_batches": float(len(batches)),
-            "weight_wait_s": pf.take_wait_seconds(), "weight_h2d_bytes": 0.0,
-            "act_d2h_bytes": 0.0, "act_h2d_bytes": 0.0, "resumed_from_shard": 0.0,
-            "graph_captures": float(graphs.captures), "graph_replays": float(graphs.replays),
-            "speculative": 0.0,
-        }
-        return outputs
-
-    def _pick_rows(self, batch: PackedBatch, probs: torch.Tensor, step: int) -> torch.Tensor:
-        """[rows] int32 on the device: the next token of every suffix of ``batch``.  Greedy: the
-        row argmax.  Sampling: ``ops.sample_rows`` with the batch's draws for generation step
-        ``step`` (they depend on no data: a small pinned H2D on the current stream, no
-        synchronisation)."""
-        if self.sampling is None:
-            return self.ops.argmax_rows(probs)
-        d = sample_draws(self.sampling.seed, [self.prompt_base + int(p) for p in batch.prompt_ids],
-                         batch.n_suffix, step)
-        host = torch.from_numpy(d.view(np.int64))
-        if self.cuda:
-            # (a pinned tensor of the caching host allocator: not reused before the copy ran)
-            pinned = torch.empty(host.shape, dtype=torch.int64, pin_memory=True)
-            pinned.copy_(host)
-            host = pinned.to(self.dev, non_blocking=True)
-        return self.ops.sample_rows(probs, self._sample_table, host, self.sampling.top_k, self.sampling.P)
+        return self._collect_graphed(pending, res, batches, t_start, flops, graphs, pf.take_wait_seconds())
 
     def _enqueue_graphed(self, batches, run, step: Optional[int] = None):
-        """Replay every micro-batch (``run(batch, index) -> probs``), its row argmax (sampling: the
-        tokens drawn for generation step ``step``, default this call's) and the D2H of both into
-        pooled pinned buffers, all on the current stream -> (pending, token tensors, decoder
-        FLOPs)."""
+        """Replay every micro-batch (``run(batch, index) -> probs``), then its picked tokens (sampling:
+        those drawn for generation step ``step``, default this call's) and the D2H of both, all on
+        the current stream (``Outputs.start``) -> (pending, decoder FLOPs)."""
         step = self.sample_step if step is None else step
-        store = self._get_store()
-        pending, ams, flops = [], [], 0.0
+        pending, flops = [], 0.0
         for i, batch in enumerate(batches):
-            probs = run(batch, i)
-            am = self._pick_rows(batch, probs, step)
-            if self.score_top_k:
-                # the K best entries and the tokens' probabilities instead of the rows themselves
-                host, pool_buf = self._topk_to_host(probs, am, None)
-                pending.append((batch, host, pool_buf, None))
-            else:
-                nbytes = probs.numel() * probs.element_size()
-                pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])
-                host = pool_buf[:nbytes].view(probs.dtype).view(probs.shape)
-                host_am = pool_buf[nbytes:nbytes + 4 * probs.shape[0]].view(torch.int32)
-                host.copy_(probs, non_blocking=True)     # same stream: ordered before the next replay
-                host_am.copy_(am, non_blocking=True)
-                pending.append((batch, host, pool_buf, host_am))
-            ams.append(am)
+            pending.append(self.out.start(batch, run(batch, i), step, None, self.prompt_base))
             # every unpruned decoder layer has the same count: one evaluation each way (80 per step
             # cost 3.4 ms of host time, on the path that must stay under a generation step's GPU time)
             pruned = [self._pruned(n) for n in self.names if layer_kind(n) == "decoder"]
@@ -1321,16 +1244,37 @@ class ShardedRunner:
             flops += (len(pruned) - n_pruned) * layer_flops(self.cfg, batch, False)
             if n_pruned:
                 flops += n_pruned * layer_flops(self.cfg, batch, True)
-        return pending, ams, flops
+        return pending, flops
 
-    def _collect_graphed(self, pending, outputs, n_prompts: int) -> None:
-        store = self._get_store()
-        self.last_tokens = [None] * n_prompts
-        self.last_token_probs = [None] * n_prompts
-        self.score_d2h_bytes = 0
-        for batch, host, pool_buf, host_am in pending:
-            self._collect(batch, host.numpy(), host_am, outputs)
-            store.recycle_host(pool_buf)
+    def _collect_graphed(self, pending, res: CallResults, batches, t_start: float, flops: float, graphs,
+                         weight_wait_s: float = 0.0, **spec_stats) -> List[Optional[np.ndarray]]:
+        """A graphed step whose copies have finished: its results and statistics (a step enqueued
+        behind it learns the tokens it assumed)."""
+        self.out.collect(pending, res)
+        if self._spec is not None:
+            self._spec["prev_tokens"] = list(res.tokens)
+        wall = time.perf_counter() - t_start
+        self.stats = {
+            "wall_s": wall, "compute_launch_s": wall,
+            "tokens": float(sum(b.num_tokens for b in batches)),
+            "padded_tokens": float(sum(b.padded_tokens for b in batches)),
+            "decoder_flops": flops, "micro_batches": float(len(batches)),
+            "weight_wait_s": weight_wait_s, "weight_h2d_bytes": 0.0,
+            "act_d2h_bytes": 0.0, "act_h2d_bytes": 0.0, "resumed_from_shard": 0.0,
+            "graph_captures": float(graphs.captures), "graph_replays": float(graphs.replays),
+            "speculative": 0.0, **spec_stats,
+        }
+        return self._publish(res)
+
+    def _publish(self, res: CallResults) -> List[Optional[np.ndarray]]:
+        """A call's results onto the runner (before the first call: empty) -> its outputs."""
+        self.last_tokens = res.tokens                  # the picked (greedy or sampled) token per suffix
+        self.last_token_probs = res.token_probs        # score_top_k: their probabilities, fp16 [n_s, 1] per prompt
+        self.last_accept = res.accept                  # drafted calls: accepted draft tokens, [n_s] int64 per prompt
+        self.last_token_logprobs = res.token_logprobs  # loglik: per prompt a list of n_s float32 arrays
+        self.score_d2h_bytes = res.d2h_bytes           # bytes of scores the call copied to the host
+        self.lookup_rows, self.lookup_kept = res.lookup_rows, res.lookup_kept   # rows drafted calls scored / kept
+        return res.outputs
 
     # ------------------------------------------------- speculative generation steps
     # A greedy generation step re-tokenizes ``suffix + decode(tokens)`` (main.py:86-88), which
@@ -1345,7 +1289,8 @@ class ShardedRunner:
     # recomputes every row from the first differing token, overwriting the speculative rows).
     spec_steps = 0
 
-    def _launch_spec(self, tps, entry, batches, ams) -> Optional[dict]:
+    def _launch_spec(self, tps, entry, batches, prev) -> Optional[dict]:
+        """``prev``: this step's pending outputs, whose picked tokens are the next step's new ids."""
         if not (knobs.get_int("FLS_SPEC_DECODE") and self._decode_graphs is not None
                 and all(b.work2 is not None and b.num_tokens == b.n_scored for b in batches)):
             return None
@@ -1373,13 +1318,13 @@ class ShardedRunner:
             pe, self.ctx.prefix_entry = self.ctx.prefix_entry, entry     # (a capture's eager forward reads it)
             try:
                 # (sampling: the speculative step is generation step sample_step + 1)
-                pending, ams2, flops = self._enqueue_graphed(sb, lambda b, i: graphs.run(b, entry, ids_dev=ams[i]),
-                                                             step=self.sample_step + 1)
+                pending, flops = self._enqueue_graphed(sb, lambda b, i: graphs.run(b, entry, ids_dev=prev[i].picked),
+                                                       step=self.sample_step + 1)
             finally:
                 self.ctx.prefix_entry = pe
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(self.dev))
-            return {"tps": spec_tps, "entry": entry, "rows": rows, "batches": sb, "pending": pending, "ams": ams2,
+            return {"tps": spec_tps, "entry": entry, "rows": rows, "batches": sb, "pending": pending,
                     "flops": flops, "done": done, "prev_tokens": None, "t0": time.perf_counter()}
         except Exception:
             return None
@@ -1399,42 +1344,28 @@ class ShardedRunner:
                     return False
         return True
 
-    def _finish_spec(self, spec: dict, tps, t_start: float) -> List[Optional[np.ndarray]]:
+    def _finish_spec(self, spec: dict, tps, t_start: float, res: CallResults) -> List[Optional[np.ndarray]]:
         entry = spec["entry"]
         if self.spec_steps > 0:
             ws, self.ctx.ws = self.ctx.ws, None
             try:
-                self._spec = self._launch_spec(tps, entry, spec["batches"], spec["ams"])
+                self._spec = self._launch_spec(tps, entry, spec["batches"], spec["pending"])
             finally:
                 self.ctx.ws = ws
         spec["done"].synchronize()
-        outputs: List[Optional[np.ndarray]] = [None] * len(tps)
-        self._collect_graphed(spec["pending"], outputs, len(tps))
-        if self._spec is not None:
-            self._spec["prev_tokens"] = list(self.last_tokens)
         entry.complete = True
         entry.commit_suffixes(tps, spec["rows"])
         self.prefix_cache.hits += 1
-        wall = time.perf_counter() - t_start
-        graphs = self._decode_graphs
-        batches = spec["batches"]
-        self.stats = {
-            "wall_s": wall, "compute_launch_s": wall,
-            "tokens": float(sum(b.num_tokens for b in batches)),
-            "padded_tokens": float(sum(b.padded_tokens for b in batches)),
-            "decoder_flops": spec["flops"], "micro_batches": float(len(batches)),
-            "weight_wait_s": 0.0, "weight_h2d_bytes": 0.0, "act_d2h_bytes": 0.0, "act_h2d_bytes": 0.0,
-            "resumed_from_shard": 0.0, "graph_captures": float(graphs.captures),
-            "graph_replays": float(graphs.replays), "speculative": 1.0, "prefix_cached": 1.0,
-            "suffix_tokens_reused": float(sum(len(s) - 1 for tp in tps for s in tp.suffixes)), "host_pack_s": 0.0,
-        }
-        return outputs
+        return self._collect_graphed(
+            spec["pending"], res, spec["batches"], t_start, spec["flops"], self._decode_graphs, speculative=1.0,
+            prefix_cached=1.0, suffix_tokens_reused=float(sum(len(s) - 1 for tp in tps for s in tp.suffixes)),
+            host_pack_s=0.0)
 
     def _drop_spec(self, spec: dict) -> None:
         spec["done"].synchronize()
         store = self._get_store()
-        for _, _, pool_buf, _ in spec["pending"]:
-            store.recycle_host(pool_buf)
+        for p in spec["pending"]:
+            store.recycle_host(p.pool_buf)
         self.spec_dropped += 1
 
     spec_dropped = 0
@@ -1505,265 +1436,6 @@ class ShardedRunner:
         if k0 and self.verbose:
             print(f"rank{self.comm.rank}: resuming at shard {k0} from {ck.dir}")
         return ck, k0, (ck.load(k0) if k0 else {})
-
-    def _collect(self, batch: PackedBatch, probs: np.ndarray, am, outputs) -> None:
-        """Host scores of a finished micro-batch into ``outputs`` (prompt order) and its greedy
-        tokens into ``self.last_tokens`` (``am``: the rows' argmax, computed on the device)."""
-        if isinstance(am, dict):
-            return self._collect_lookup(batch, probs, am, outputs)
-        self.score_d2h_bytes += probs.nbytes + (4 * am.numel() if am is not None else 0)
-        if self.loglik:
-            return self._collect_loglik(batch, probs, outputs)
-        if self.embed is not None:
-            return self._collect_embed(batch, probs, outputs)
-        if self.score_top_k:
-            return self._collect_topk(batch, probs, outputs)
-        am = am.numpy() if am is not None else None
-        r = 0
-        for j, pid in enumerate(batch.prompt_ids):
-            ns = batch.n_suffix[j]
-            outputs[pid] = np.expand_dims(probs[r:r + ns].astype(np.float16, copy=True), axis=1)
-            if am is not None:
-                self.last_tokens[pid] = am[r:r + ns].astype(np.int64).reshape(ns, 1)
-            r += ns
-
-    def _collect_loglik(self, batch: PackedBatch, pairs: np.ndarray, outputs) -> None:
-        """The [n_pairs, 2] (log-probability, greedy flag) rows of a finished micro-batch split back
-        into suffixes (pairs are in prompt -> suffix -> token order): per prompt the [n_s, 3] float32
-        (sum, token count, all-greedy) into ``outputs`` — sums in float64 — and the per-token
-        values into ``self.last_token_logprobs``."""
-        r = 0
-        for j, pid in enumerate(batch.prompt_ids):
-            s0, s1 = (int(v) for v in batch.prompt_scored[j])
-            lens = self._pair_lens[pid]
-            assert s0 == r and s1 - s0 == sum(lens), (s0, s1, r, lens)
-            out = np.empty((len(lens), 3), dtype=np.float32)
-            per_tok = []
-            for s, n in enumerate(lens):
-                lp = pairs[r:r + n, 0].astype(np.float32, copy=True)
-                out[s] = (lp.astype(np.float64).sum(), n, float(bool((pairs[r:r + n, 1] == 1.0).all())))
-                per_tok.append(lp)
-                r += n
-            outputs[pid] = out
-            self.last_token_logprobs[pid] = per_tok
-
-    def _collect_embed(self, batch: PackedBatch, emb: np.ndarray, outputs) -> None:
-        """The [n_suffixes, D] float32 embeddings of a finished micro-batch (prompt -> suffix order)
-        split back into prompts."""
-        assert emb.dtype == np.float32 and emb.shape == (int(sum(batch.n_suffix)), self.embed.dim), (emb.dtype, emb.shape)
-        r = 0
-        for j, pid in enumerate(batch.prompt_ids):
-            ns = batch.n_suffix[j]
-            outputs[pid] = emb[r:r + ns].copy()
-            r += ns
-
-    # ------------------------------------------------- compact scores (score_top_k)
-    def _topk_offsets(self, rows: int):
-        """Byte offsets of a micro-batch's compact scores in one host buffer: ids int32 [rows, K],
-        tokens int32 [rows], probabilities fp16 [rows, K], token probabilities fp16 [rows] (the
-        int32 parts first, so every view stays aligned) -> (tokens, probabilities, token
-        probabilities, total)."""
-        K = self.score_top_k
-        o_tok = 4 * rows * K
-        o_vals = o_tok + 4 * rows
-        o_pv = o_vals + 2 * rows * K
-        return o_tok, o_vals, o_pv, o_pv + 2 * rows
-
-    def _topk_to_host(self, probs: torch.Tensor, am: torch.Tensor, stream):
-        """``ops.topk_rows`` of a micro-batch's probabilities and its chosen tokens ``am`` on the
-        current stream (a plain launch: right behind a graph replay too), then the D2H of the four
-        small results into one pooled pinned buffer on ``stream`` (None: the current stream) ->
-        (the buffer's used bytes, the pooled buffer).  Without a GPU: (a host byte tensor, None)."""
-        rows, K = probs.shape[0], self.score_top_k
-        ids, vals, pv = self.ops.topk_rows(probs, K, picked=am)
-        parts = (ids, am, vals, pv)
-        if not self.cuda:
-            return torch.cat([p.detach().cpu().contiguous().reshape(-1).view(torch.uint8) for p in parts]), None
-        o_tok, o_vals, o_pv, total = self._topk_offsets(rows)
-        pool_buf = self._get_store().host_buffer(total)
-        views = (pool_buf[:o_tok].view(torch.int32).view(rows, K), pool_buf[o_tok:o_vals].view(torch.int32),
-                 pool_buf[o_vals:o_pv].view(torch.float16).view(rows, K), pool_buf[o_pv:total].view(torch.float16))
-        if stream is None:
-            for h, d in zip(views, parts):
-                h.copy_(d, non_blocking=True)        # same stream: ordered before the next replay
-        else:
-            stream.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(stream):
-                for h, d in zip(views, parts):
-                    h.copy_(d, non_blocking=True)
-                    d.record_stream(stream)
-        return pool_buf[:total], pool_buf
-
-    def _collect_topk(self, batch: PackedBatch, buf: np.ndarray, outputs) -> None:
-        """The host bytes of a finished micro-batch (``_topk_offsets``) split back into prompts:
-        per prompt a ``TOPK_DTYPE`` [n_s, 1, K] array into ``outputs``, the chosen tokens into
-        ``self.last_tokens`` and their probabilities into ``self.last_token_probs``."""
-        K = self.score_top_k
-        rows = int(sum(batch.n_suffix))
-        o_tok, o_vals, o_pv, total = self._topk_offsets(rows)
-        assert buf.dtype == np.uint8 and buf.size == total, (buf.dtype, buf.size, total)
-        ids = buf[:o_tok].view(np.int32).reshape(rows, K)
-        tok = buf[o_tok:o_vals].view(np.int32)
-        vals = buf[o_vals:o_pv].view(np.float16).reshape(rows, K)
-        pv = buf[o_pv:total].view(np.float16)
-        r = 0
-        for j, pid in enumerate(batch.prompt_ids):
-            ns = batch.n_suffix[j]
-            out = np.empty((ns, 1, K), dtype=TOPK_DTYPE)
-            out["id"][:, 0, :] = ids[r:r + ns]
-            out["p"][:, 0, :] = vals[r:r + ns]
-            outputs[pid] = out
-            self.last_tokens[pid] = tok[r:r + ns].astype(np.int64).reshape(ns, 1)
-            self.last_token_probs[pid] = pv[r:r + ns].copy().reshape(ns, 1)
-            r += ns
-
-    # ------------------------------------------------- prompt-lookup drafts (run_tokenized(drafts=...))
-    def _start_lookup_copy(self, batch: PackedBatch, probs: torch.Tensor):
-        """A drafted micro-batch's output: ``ops.verify_rows`` on its scored rows, then the D2H of
-        the KEPT rows only (gathered by ``copy_rows`` into a compact device buffer, from there
-        into the pooled pinned buffer; ``score_top_k``: ``topk_rows`` on the kept rows).  The host
-        waits once, for the accepted counts (a few ints): they size the copy."""
-        meta = batch.device_tensors(self.dev)
-        tok, accept, keep, n_kept = self.ops.verify_rows(probs, meta["row_start"], meta["draft"])
-        n_sfx = accept.shape[0]
-        if self.cuda:
-            # accept and n_kept are one [n_sfx + 1] vector on the device (ops.verify_rows): one copy
-            # into a pooled pinned buffer, and the host waits for that copy alone
-            dev_ctrl = accept.as_strided((n_sfx + 1,), (1,))
-            assert dev_ctrl[n_sfx:].data_ptr() == n_kept.data_ptr()
-            ctrl_buf = self._get_store().host_buffer(4 * (n_sfx + 1))
-            ctrl = ctrl_buf[:4 * (n_sfx + 1)].view(torch.int32)
-            ctrl.copy_(dev_ctrl, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.dev))
-            done.synchronize()
-        else:
-            ctrl_buf, ctrl = None, torch.cat([accept, n_kept]).cpu()
-        acc = ctrl[:n_sfx].numpy().astype(np.int64)
-        nk = int(ctrl[n_sfx])
-        if ctrl_buf is not None:
-            self._get_store().recycle_host(ctrl_buf)
-        if nk != int(acc.sum()) + n_sfx:
-            raise RuntimeError(f"verify_rows kept {nk} rows for accepted counts summing to {int(acc.sum())} "
-                               f"over {n_sfx} suffixes")
-        idx = keep[:nk]
-        kept = self._gather_kept(probs, idx)                     # [kept, V]: what crosses PCIe
-        tok_k = tok.index_select(0, idx.long()).contiguous()
-        extra = {"accept": acc, "rows": int(probs.shape[0]), "kept": nk}
-        if self.score_top_k:
-            host, pool_buf = self._topk_to_host(kept, tok_k, self.d2h_stream)
-            ev = None
-            if self.cuda:
-                ev = torch.cuda.Event()
-                ev.record(self.d2h_stream)
-            return batch, host, ev, pool_buf, extra
-        if not self.cuda:
-            extra["tok"] = tok_k.cpu().numpy()
-            return batch, kept.detach().to(torch.float16).cpu(), None, None, extra
-        store = self._get_store()
-        nbytes = kept.numel() * kept.element_size()
-        pool_buf = store.host_buffer(nbytes + 4 * nk)
-        host = pool_buf[:nbytes].view(kept.dtype).view(kept.shape)
-        host_tok = pool_buf[nbytes:nbytes + 4 * nk].view(torch.int32)
-        self.d2h_stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.d2h_stream):
-            host.copy_(kept, non_blocking=True)
-            kept.record_stream(self.d2h_stream)
-            host_tok.copy_(tok_k, non_blocking=True)
-            tok_k.record_stream(self.d2h_stream)
-            ev = torch.cuda.Event()
-            ev.record(self.d2h_stream)
-        extra["tok"] = host_tok
-        return batch, host, ev, pool_buf, extra
-
-    def _gather_kept(self, probs: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-        """probs[idx] as a compact [len(idx), V] tensor: ``copy_rows`` (16 bytes per lane) where the
-        rows allow it, ``index_select`` for a vocabulary that is no multiple of 8 (Granite's 49,155)."""
-        if probs.shape[1] % 8 == 0 and probs.stride(0) % 8 == 0 and probs.data_ptr() % 16 == 0:
-            return self.ops.gather_rows(probs, idx)
-        return probs.index_select(0, idx.long())
-
-    def _collect_lookup(self, batch: PackedBatch, host: np.ndarray, extra: dict, outputs) -> None:
-        """A drafted micro-batch's kept rows split back into prompts and suffixes: per prompt a
-        list of [kept, V] fp16 (``score_top_k``: ``TOPK_DTYPE`` [kept, K]) arrays into ``outputs``,
-        of [kept] int64 tokens into ``last_tokens`` (and fp16 probabilities into
-        ``last_token_probs``), and the accepted counts into ``last_accept``."""
-        acc, nk, K = extra["accept"], extra["kept"], self.score_top_k
-        self.lookup_rows += extra["rows"]
-        self.lookup_kept += nk
-        self.score_d2h_bytes += host.nbytes + (0 if K else 4 * nk)
-        pv = None
-        if K:
-            o_tok, o_vals, o_pv, total = self._topk_offsets(nk)
-            assert host.dtype == np.uint8 and host.size == total, (host.dtype, host.size, total)
-            ids = host[:o_tok].view(np.int32).reshape(nk, K)
-            tok = host[o_tok:o_vals].view(np.int32)
-            vals = host[o_vals:o_pv].view(np.float16).reshape(nk, K)
-            pv = host[o_pv:total].view(np.float16)
-        else:
-            tok = extra["tok"]
-            tok = tok.numpy() if isinstance(tok, torch.Tensor) else tok
-            assert host.shape[0] == nk, (host.shape, nk)
-        r = i = 0
-        for j, pid in enumerate(batch.prompt_ids):
-            ns = batch.n_suffix[j]
-            outs, toks, pvs = [], [], []
-            for a in acc[i:i + ns]:
-                n = int(a) + 1
-                if K:
-                    out = np.empty((n, K), dtype=TOPK_DTYPE)
-                    out["id"], out["p"] = ids[r:r + n], vals[r:r + n]
-                    pvs.append(pv[r:r + n].copy())
-                else:
-                    out = host[r:r + n].astype(np.float16, copy=True)
-                outs.append(out)
-                toks.append(tok[r:r + n].astype(np.int64))
-                r += n
-            outputs[pid] = outs
-            self.last_tokens[pid] = toks
-            self.last_token_probs[pid] = pvs if K else None
-            self.last_accept[pid] = acc[i:i + ns].copy()
-            i += ns
-        assert r == nk and i == acc.shape[0], (r, nk, i, acc.shape)
-
-    def _start_output_copy(self, batch: PackedBatch, probs: torch.Tensor):
-        """D2H of a micro-batch's probabilities and of their row argmax (the greedy token of
-        each suffix: api.generation_loop needs no host pass over the [n_s, V] scores).
-        ``score_top_k``: of the K best entries and the tokens' probabilities instead.
-        A drafted micro-batch (prompt-lookup decoding): of its kept rows (``_start_lookup_copy``)."""
-        if batch.draft is not None:
-            return self._start_lookup_copy(batch, probs)
-        if self.score_top_k:
-            am = self._pick_rows(batch, probs, self.sample_step)
-            host, pool_buf = self._topk_to_host(probs, am, self.d2h_stream)
-            if not self.cuda:
-                return batch, host, None, None, None
-            ev = torch.cuda.Event()
-            ev.record(self.d2h_stream)
-            return batch, host, ev, pool_buf, None
-        fp32 = self.loglik or self.embed is not None
-        if fp32:
-            am = None                 # probs: the fp32 [n_pairs, 2] head state (embed: the [n_sfx, D] norm
-            #                           state), copied as it is
-        else:
-            am = self._pick_rows(batch, probs, self.sample_step) if hasattr(self.ops, "argmax_rows") else None
-        if not self.cuda:
-            return batch, probs.detach().to(torch.float32 if fp32 else torch.float16).cpu(), None, None, am
-        store = self._get_store()
-        nbytes = probs.numel() * probs.element_size()
-        pool_buf = store.host_buffer(nbytes + 4 * probs.shape[0])
-        host = pool_buf[:nbytes].view(probs.dtype).view(probs.shape)
-        host_am = pool_buf[nbytes:nbytes + 4 * probs.shape[0]].view(torch.int32)
-        self.d2h_stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.d2h_stream):
-            host.copy_(probs, non_blocking=True)
-            probs.record_stream(self.d2h_stream)
-            if am is not None:
-                host_am.copy_(am, non_blocking=True)
-                am.record_stream(self.d2h_stream)
-            ev = torch.cuda.Event()
-            ev.record(self.d2h_stream)
-        return batch, host, ev, pool_buf, (host_am if am is not None else None)
 
     def close(self):
         if self._spec is not None:             # an enqueued speculative step finishes first

@@ -5,7 +5,8 @@ finds the latest earlier occurrence of the text's last n-gram and proposes the t
 it; one call of the model then scores the suffix's last token and every draft token
 (``ShardedRunner.run_tokenized(..., drafts=...)``), and :func:`verify_rows` — the host definition of
 ``ops.verify_rows`` / the ``fls_verify_rows`` kernel (``csrc/kernels/lookup.hip``) — keeps the draft
-tokens the greedy decoding would have produced itself.
+tokens the greedy decoding would have produced itself.  Only the kept rows are copied to the host and
+split back into suffixes (``runtime/outputs.py``, ``Outputs._start_drafted``).
 
 With the prefix K/V cache every call is row-exact (``engine.py`` "exact K/V reuse"): a row's scores
 do not depend on the rows that share its call, so the scores of an accepted draft position are bit

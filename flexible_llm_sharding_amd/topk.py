@@ -5,7 +5,8 @@ probable ``(token id, fp16 probability)`` pairs in rank order, and the id and pr
 token the engine chose for the row (greedy or sampled).  The probabilities on the device, the chosen
 tokens and the updated prompts are those of the same run without the flag.  Device kernel
 (``csrc/kernels/topk.hip``), this host implementation and the test oracle return the same entries
-for every input.
+for every input.  ``runtime/outputs.py`` packs the entries for the host (``Outputs._compact``) and
+splits them back into prompts.
 
 1. A row is V fp16 bit patterns ``b_i``.
 2. The key of entry i is ``k_i = b_i`` if ``b_i <= 0x3C00`` (0 to 1.0), else 0: negative, NaN and

@@ -252,7 +252,7 @@ def test_kept_rows_gather_for_any_vocabulary(tiny_model, V):
     try:
         x = torch.rand(11, V, device=DEV).half()
         idx = torch.tensor([0, 3, 4, 10, 7], dtype=torch.int32, device=DEV)
-        got = r._gather_kept(x, idx)
+        got = r.out.gather_kept(x, idx)
         torch.cuda.synchronize()
         assert tuple(got.shape) == (5, V) and got.is_contiguous()
         assert torch.equal(got.cpu(), x.cpu()[idx.cpu().long()])

@@ -141,7 +141,7 @@ def test_engine_compact_scores_equal_oracle_on_full_scores(setup, K):
 
 def test_engine_scoring_pass_and_streamed_weights(setup):
     """One scoring pass, and a generation whose weights are not resident (the pass through
-    ``_start_output_copy``)."""
+    ``Outputs.start`` on the D2H stream)."""
     tr.check_compact_run(_full(setup, "score", num_gen=1), tr.generate(setup, CPU, top_k=20, num_gen=1), 20)
     kw = dict(num_gen=2, resident=False, prefix_kv_cache=False, suffix_kv_cache=False)
     tr.check_compact_run(_full(setup, "streamed", **kw), tr.generate(setup, CPU, top_k=5, **kw), 5)
