@@ -96,6 +96,16 @@ int fls_row_rstd(const void* x, int ldx, const int* row_idx, int rows, int H, fl
 // W[n, k] = fp16(W[n, k] * gamma[k]) in place for n < N, k < K (the RMSNorm weight folded into
 // the projection that consumes the normed rows)
 int fls_fold_norm(void* w, int ldw, int N, int K, const void* gamma, fls_stream_t s);
+// LoRA merge in place (csrc/kernels/lora.hip; the definition: flexible_llm_sharding_amd/lora.py):
+//   W[o, i] = fp16_rne(fmaf(Bs[o, R-1], A[R-1, i], ... fmaf(Bs[o, 0], A[0, i], fp32(W[o, i])) ...))
+// k ascending, one fp32 rounding per product, R = r rounded up to a multiple of 4.  W: fp16
+// [rows, cols] contiguous, any 2-byte aligned address (16-byte accesses when cols % 8 == 0 and W is
+// 16-byte aligned, else 2-byte ones); A: fp32 [R, cols]; Bs: fp32 [rows, R] (the scale folded in),
+// both padded to R with +0 by the caller and 4-byte aligned.  Nothing outside W's rows * cols
+// elements is written.  Returns hipErrorInvalidValue (1), with nothing launched, for a null pointer,
+// rows <= 0, cols <= 0, rows or cols >= 2^31 (or more than 2^33 tiles of 32 x 64), r outside 1..256, or
+// a misaligned pointer.
+int fls_lora_merge(void* W, long long rows, long long cols, const void* A, const void* Bs, int r, fls_stream_t s);
 // y[dst_idx[r]] = x[src_idx[r]] for r < rows (fp16 rows of H elements; a null index = identity)
 // device-to-device copy: mode 0 HIP runtime (blit kernel), 1 SDMA engines (no CU), 2 `blocks` workgroups
 int fls_copy_d2d(void* dst, const void* src, uint64_t bytes, int mode, int blocks, fls_stream_t s);

@@ -87,7 +87,18 @@ def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str
     return "host" if fits else "stream"
 
 
-def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device):
+def load_lora(args, cfg: ModelConfig):
+    """``--lora DIR`` (``--lora_scale X``) -> the loaded adapter (lora.LoraAdapter), or None."""
+    from .utils.cli import check_lora
+    check_lora(args)
+    if not getattr(args, "lora", None):
+        return None
+    from .lora import LoraAdapter
+    scale = getattr(args, "lora_scale", None)
+    return LoraAdapter.load(cfg, args.lora, 1.0 if scale is None else float(scale))     # (0 is a scale)
+
+
+def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device, lora=None):
     # (embed mode ends at model.norm: the LM head is neither planned nor read, and need not exist)
     names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
     plan = make_plan(len(names), args.layer_num_per_shard, comm.world, comm.rank, args.data_parallel,
@@ -113,6 +124,8 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device):
         from .runtime.weights import CompactHostStore
         return CompactHostStore(src, pinned=device.type == "cuda")
     st = HostStore.from_source(src, pinned=device.type == "cuda", names=mine)
+    if lora is not None:
+        st.merge_lora(lora, device)        # once, before the fold: (W + sBA) diag(norm)
     return st.fold_norms(device) if fold else st
 
 
@@ -231,6 +244,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     if mode == "embed":
         ep = EmbedParams.from_args(args)
         embed_kw = dict(embed_pooling=ep.pooling, embed_dim=ep.dim, embed_normalize=ep.normalize)
+    lora = load_lora(args, cfg)
     pkv = resolve_prefix_kv_cache(args)
     skv = resolve_suffix_kv_cache(args, comm.world) and pkv
     n_dec = sum(1 for n in cfg.layer_names() if layer_kind(n) == "decoder")
@@ -263,8 +277,8 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                 args = copy.copy(args)
                 args.resident = True
         wc = resolve_weight_cache(args, cfg, comm, mode_layer_names(cfg, mode), sliced=True)
-        return build_dp_sharded_runner(args, cfg, device, comm, tok, weight_cache=wc, prefix_kv_cache=pkv)
-    src = build_source(args, cfg, comm, device)
+        return build_dp_sharded_runner(args, cfg, device, comm, tok, weight_cache=wc, prefix_kv_cache=pkv, lora=lora)
+    src = build_source(args, cfg, comm, device, lora)
     act = None
     if args.dtype:
         act = torch.float16 if args.dtype == "float16" else torch.float32
@@ -290,7 +304,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          # one rank draws the tokens on the device; several ranks: rank 0 draws the
                          # same tokens on the host from the gathered scores (generation_loop)
                          sampling=SamplingParams.from_args(args) if comm.world == 1 else None,
-                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), **embed_kw)
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), lora=lora, **embed_kw)
 
 
 def load_model_meta(args):
@@ -679,6 +693,9 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
                                        else getattr(src, "total_bytes", 0))
     metrics["fp8_tensors"] = int(files.fp8_tensors()) if hasattr(files, "fp8_tensors") else 0
     metrics["int4_tensors"] = int(files.int4_tensors()) if hasattr(files, "int4_tensors") else 0
+    ad = getattr(runner, "lora", None)
+    metrics.update({"lora_tensors": int(ad.n_tensors) if ad else 0, "lora_rank_max": int(ad.rank_max) if ad else 0,
+                    "lora_bytes": int(ad.nbytes) if ad else 0, "lora_merge_launches": int(ad.merge_launches) if ad else 0})
     metrics["weight_pinned_bytes"] = int(src.pinned_bytes() if hasattr(src, "pinned_bytes")
                                          else getattr(src, "total_bytes", 0))
     metrics["score_d2h_bytes_last_pass"] = int(getattr(runner, "score_d2h_bytes", 0))

@@ -86,7 +86,7 @@ class ShardedRunner:
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
                  exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token",
                  sampling=None, score_top_k: int = 0, embed_pooling: Optional[str] = None,
-                 embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None):
+                 embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None, lora=None):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
         if score_mode not in ("next_token", "loglik", "embed"):
@@ -201,6 +201,22 @@ class ShardedRunner:
             # an FP8 checkpoint's scales go to the device now (one allocation), before any memory is
             # measured for a VRAM plan
             source.prepare_device(self.dev)
+        # a LoRA adapter (lora.LoraAdapter), merged into the weights as they land: its staging buffer
+        # (the largest layer's A + Bs) is allocated now too, so a VRAM plan sees it as context
+        self.lora = lora
+        self.lora_staging = None           # this runner's own (lora.Staging), dropped in close()
+        merged = getattr(source, "lora_merged", None)
+        if merged is not None and (lora is None or merged != lora.identity):
+            raise ValueError("the weight source holds a LoRA adapter's merged weights (HostStore.merge_lora): "
+                             "only a runner with that adapter can run them")
+        if lora is not None and merged is None:
+            if getattr(source, "norms_folded", False):
+                raise ValueError("the weight source holds norm-folded weights: a LoRA adapter is merged before "
+                                 "the fold (HostStore.merge_lora, then fold_norms)")
+            if getattr(source, "lora_at_build", False):
+                source.merge_lora(lora, self.dev)          # whole fp16 layers on the host: merged once
+            else:
+                self.lora_staging = lora.new_staging(self.dev)
         # this runner's split-K / split-KV scratch (64 MB): the free tail of the activation arena —
         # split-K only runs for <= 512-row GEMMs, whose phase carves a sliver of an arena sized for
         # the whole micro-batch — or, when the arena is too small, a buffer of its own.  Every
@@ -273,10 +289,20 @@ class ShardedRunner:
         if prefolded and not self.ctx.fused_norm:
             raise ValueError("the weight source holds norm-folded weights (HostStore.fold_norms): only the "
                              "fused-norm HIP path can run them")
-        if self.ctx.fused_norm and not prefolded:
+        # what happens to a decoder layer as it lands: the LoRA merge first, then the fold — the
+        # folded weight is (W + sBA) diag(norm)
+        fold = self.ctx.fused_norm and not prefolded
+        merge = lora is not None and getattr(source, "lora_merged", None) is None
+        if fold or merge:
             from .models.llama import fold_layer_norms
-            ops = self.ops
-            self.prefetcher.on_load = lambda views: fold_layer_norms(ops, views)
+            ops, staging = self.ops, self.lora_staging
+
+            def on_load(name, views):
+                if merge:
+                    lora.merge_views(ops, name, views, staging)
+                if fold:
+                    fold_layer_norms(ops, views)
+            self.prefetcher.on_load = on_load
         self.h2d_stream = torch.cuda.Stream(self.dev) if self.cuda else None
         self.d2h_stream = torch.cuda.Stream(self.dev) if self.cuda else None
         if self.cuda:
@@ -1414,7 +1440,8 @@ class ShardedRunner:
                              lnps=self.lnps, budget=self.token_budget, attn=self.prefix_attention,
                              world=self.comm.world, rank=self.comm.rank, dp=self.data_parallel,
                              dtype=str(self.act_dtype), every=self.checkpoint_every,
-                             prune=self.ctx.prune_last, stages=self.plan.stages)
+                             prune=self.ctx.prune_last, stages=self.plan.stages,
+                             **({"lora": self.lora.identity} if self.lora is not None else {}))
         ck = RunCheckpoint(self.resume_dir, fp, self.comm.rank)
         have = set(ck.available())
         if self.plan.mode == "mp":
@@ -1451,6 +1478,9 @@ class ShardedRunner:
             self._inbox.close()
             self._inbox = None
         self.prefetcher.close()
+        if self.lora_staging is not None:
+            self.lora_staging.release()    # (the prefetcher's close synchronised the copy stream)
+            self.lora_staging = None
         if hasattr(self.src, "close"):
             self.src.close()           # the streaming source's pinned ring
         if self._store is not None:

@@ -723,6 +723,17 @@ class HipOps:
         _chk(self.k.fls_dequant_int4(region.data_ptr(), numel, group, SCALE_CODES[scale_dtype], _stream()),
              "fls_dequant_int4")
 
+    def lora_merge(self, w: torch.Tensor, a: torch.Tensor, bs: torch.Tensor, r: int) -> None:
+        """``w`` (fp16 ``[rows, cols]``, contiguous) += the adapter, in place (lora.py's definition;
+        csrc/kernels/lora.hip): ``a`` fp32 ``[R, cols]``, ``bs`` fp32 ``[rows, R]`` with the scale
+        folded in, both padded with +0 to ``R`` = ``r`` rounded up to a multiple of 4."""
+        from ..lora import check_merge_args
+        check_merge_args(w, a, bs, r)
+        if not (w.is_cuda and a.is_cuda and bs.is_cuda):
+            raise TypeError("lora_merge: expected CUDA tensors")
+        _chk(self.k.fls_lora_merge(w.data_ptr(), w.shape[0], w.shape[1], a.data_ptr(), bs.data_ptr(), int(r),
+                                   _stream()), "fls_lora_merge")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -345,6 +345,15 @@ class TorchOps:
         w = fp8.dequantize(b[numel:].to("cpu").clone().view(rows, cols), s)
         b.view(torch.float16).copy_(w.reshape(-1))
 
+    def lora_merge(self, w: torch.Tensor, a: torch.Tensor, bs: torch.Tensor, r: int) -> None:
+        """``w`` (fp16 ``[rows, cols]``) += the adapter, in place, by the host definition
+        (lora.merge_reference): ``a`` fp32 ``[R, cols]``, ``bs`` fp32 ``[rows, R]`` with the scale
+        folded in, both padded with +0 to ``R`` = ``r`` rounded up to a multiple of 4."""
+        from .. import lora
+        lora.check_merge_args(w, a, bs, r)
+        out = lora.merge_reference(w.detach().to("cpu"), a[:r].to("cpu"), bs[:, :r].to("cpu"), None)
+        w.copy_(torch.from_numpy(out).to(w.device))
+
     def dequant_int4(self, region: torch.Tensor, numel: int, group: int, scale_dtype: torch.dtype) -> None:
         """The INT4 tensor of ``numel`` weights that landed in its ``2 * numel``-byte ``region``
         (int4.region_layout) -> fp16 in place, by the host definition (int4.dequantize)."""

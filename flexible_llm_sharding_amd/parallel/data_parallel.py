@@ -86,6 +86,11 @@ class SlicedHostStore(HostStore):
         st.norms_folded = base.norms_folded
         return st
 
+    lora_at_build = False           # a slice cannot be merged alone: the gathered layer is, as it lands
+
+    def merge_lora(self, adapter, device):   # pragma: no cover - a slice cannot be merged alone
+        raise RuntimeError("a sliced store holds 1/G of each layer: the adapter is merged as each layer is gathered")
+
     def fold_norms(self, device):   # pragma: no cover - a slice cannot be folded alone
         raise RuntimeError("a sliced store holds 1/G of each layer: fold before slicing (synthetic(fold_norms=True))")
 
@@ -254,8 +259,7 @@ class AllGatherPrefetcher(ShardPrefetcher):
                     off += _align(p.chunk * G)
                     self.bytes_h2d += hi - lo
                 views[name] = piece_views(self.store.layout(name), regions, self.dtype)
-                if self.cuda:
-                    self._loaded(name, views[name])
+                self._loaded(name, views[name])      # (the gathered copy in the slot: on the CPU too)
             if self.cuda:
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
@@ -316,7 +320,7 @@ class _nullctx:
 
 
 def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[LayerSource] = None,
-                            weight_cache: str = "host", prefix_kv_cache: Optional[bool] = None):
+                            weight_cache: str = "host", prefix_kv_cache: Optional[bool] = None, lora=None):
     """Data-parallel runner with scatter-loaded weights: ``weight_cache`` ``host`` pins this
     rank's slices (read once), ``stream`` re-reads them from the layer files every pass."""
     from ..config import MAX_TOKEN_LEN
@@ -368,7 +372,7 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
                          score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None),
-                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), **embed_kw)
+                         score_top_k=int(getattr(args, "score_top_k", 0) or 0), lora=lora, **embed_kw)
 
 
 def _suffix_kv(args, comm: Comm) -> bool:

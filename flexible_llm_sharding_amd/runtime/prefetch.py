@@ -68,14 +68,15 @@ def choose_kept_shards(sizes: Sequence[int], budget: int) -> List[int]:
 
 
 class ShardPrefetcher:
-    # transform of a freshly loaded decoder layer (its weight views), enqueued on the copy stream
-    # before the load's ready event: the engine folds the input RMSNorm into W_qkv here
-    # (models.llama.fold_layer_norms), so a resident / kept shard is folded exactly once
+    # transform of a freshly loaded decoder layer (its name and weight views), enqueued on the copy
+    # stream before the load's ready event: the engine merges a LoRA adapter (lora.py) and then
+    # folds the input RMSNorm into W_qkv here (models.llama.fold_layer_norms), so a resident / kept
+    # shard is transformed exactly once
     on_load = None
 
     def _loaded(self, name: str, views: Dict[str, torch.Tensor]) -> None:
         if self.on_load is not None and layer_kind(name) == "decoder":
-            self.on_load(views)
+            self.on_load(name, views)
 
     def __init__(self, source: LayerSource, layer_names: Sequence[str],
                  shards: Sequence[Tuple[int, ...]], device, n_slots: int = 2,
@@ -195,10 +196,13 @@ class ShardPrefetcher:
             for i in self.shards[k]:
                 name = self.names[i]
                 hb = self.src.host_buffer(name)
-                if hb is None:
+                fresh = hb is None
+                if fresh:
                     hb = torch.empty(self.src.nbytes(name), dtype=torch.uint8)
                     self.src.read_into(name, hb)
                 views[name] = self.src.layout(name).views(hb, self.dtype)
+                if fresh:          # (a host store's own buffers are transformed once, by the store)
+                    self._loaded(name, views[name])
             self.load_seconds += time.perf_counter() - t0
             return None, views, s
         slot = self._slot(s)

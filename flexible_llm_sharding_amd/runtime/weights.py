@@ -64,12 +64,50 @@ class HostStore(LayerSource):
     the fused-norm engine streams them as they are — no per-load fold on the copy stream."""
 
     norms_folded = False
+    # identity of the LoRA adapter merged into the buffers (lora.LoraAdapter.identity), or None;
+    # lora_at_build: the store holds whole fp16 layers, so an adapter is merged once (merge_lora)
+    lora_merged = None
+    lora_at_build = True
 
     def __init__(self, cfg: ModelConfig, dtype=torch.float16, pinned: bool = True,
                  names: Optional[Sequence[str]] = None):
         self.cfg, self.dtype, self.pinned = cfg, dtype, pinned
         self.names = list(names) if names is not None else cfg.layer_names()
         self.buffers: Dict[str, torch.Tensor] = {}
+
+    def merge_lora(self, adapter, device) -> "HostStore":
+        """Merge a LoRA adapter (lora.LoraAdapter) into every decoder layer it targets, on
+        ``device``: each layer goes H2D, is merged, and comes back (on the CPU: in place, by the host
+        definition).  Once per store and before :meth:`fold_norms` — the folded weight is
+        ``(W + sBA) diag(norm)``; passes then cost nothing extra."""
+        from ..ops import get_ops
+        if self.lora_merged is not None:
+            if self.lora_merged != adapter.identity:
+                raise ValueError("the host store already holds another LoRA adapter's merged weights")
+            return self
+        if self.norms_folded:
+            raise ValueError("the host store's norms are folded already: merge the LoRA adapter before fold_norms")
+        if self.dtype != torch.float16:
+            raise TypeError(f"a LoRA adapter merges into fp16 weights, the store holds {self.dtype}")
+        dev = torch.device(device)
+        ops = get_ops(dev)
+        dec = [n for n in self.names if n in self.buffers and adapter.targets(n)]
+        if dec and dev.type == "cuda":
+            stage = torch.empty(max(self.nbytes(n) for n in dec), dtype=torch.uint8, device=dev)
+            ab = adapter.new_staging(dev)  # (this merge's own: passes need none, nothing is left to merge)
+            for n in dec:
+                buf = self.buffers[n]
+                full = stage[:buf.numel()]
+                full.copy_(buf)
+                adapter.merge_views(ops, n, self.layout(n).views(full, self.dtype), ab)
+                buf.copy_(full)
+            torch.cuda.synchronize(dev)
+            del stage, ab
+        else:
+            for n in dec:
+                adapter.merge_views(ops, n, self.layout(n).views(self.buffers[n], self.dtype))
+        self.lora_merged = adapter.identity
+        return self
 
     def fold_norms(self, device) -> "HostStore":
         """Fold the RMSNorm weights into the projections (models.llama.fold_layer_norms) for

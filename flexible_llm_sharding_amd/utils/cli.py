@@ -163,6 +163,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="activation dtype (default fp16 on GPU, fp32 on CPU)")
     p.add_argument("--verbose", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--metrics_json", type=str, default=None, help="write run metrics here (rank 0)")
+    p.add_argument("--lora", type=str, default=None, metavar="DIR",
+                   help="a LoRA adapter in PEFT's saved form (adapter_config.json + adapter_model.safetensors), merged "
+                        "into the weights in HBM as they land (W += s B A, lora.py); the base checkpoint is read as it "
+                        "is, fp16 / bf16, FP8 or INT4")
+    p.add_argument("--lora_scale", type=float, default=None,
+                   help="multiplies the adapter's scale alpha / r (default 1.0; needs --lora)")
     p.add_argument("--max_token_len", type=int, default=None,
                    help="token cap per prefix / suffix (reference: 4096, utils.py:14); also sizes the RoPE tables")
     p.add_argument("--synthetic", type=str, default=None, metavar="PRESET",
@@ -218,6 +224,23 @@ def check_embed(args, hidden_size: int = 0) -> None:
                       (getattr(args, "resume_dir", None), "--resume_dir")):
         if bad:
             raise ValueError(f"--score_mode embed does not combine with {flag}")
+
+
+def check_lora(args) -> None:
+    """``--lora`` / ``--lora_scale``: one adapter directory, no scale without an adapter, and no
+    adapter on ``--synthetic`` weights; a ``ValueError`` names the flag."""
+    path, scale = getattr(args, "lora", None), getattr(args, "lora_scale", None)
+    if scale is not None and not path:
+        raise ValueError("--lora_scale needs --lora")
+    if not path:
+        return
+    if isinstance(path, (list, tuple)):
+        raise ValueError("--lora takes one adapter directory")
+    if getattr(args, "synthetic", None):
+        raise ValueError("--lora does not combine with --synthetic: there are no files to adapt, and the synthetic "
+                         "store folds its norms as it generates")
+    if scale is not None and not (scale == scale and abs(scale) != float("inf")):
+        raise ValueError(f"--lora_scale {scale!r}: not finite")
 
 
 def check_sampling(args) -> None:
@@ -283,4 +306,5 @@ def parse_args(argv=None):
     check_sampling(args)
     check_top_k(args)
     check_lookup(args)
+    check_lora(args)
     return args

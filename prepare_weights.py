@@ -8,6 +8,8 @@
                  (decoder projection weights as FP8 e4m3 + fp32 scales: half the weight bytes)
                  --quantize int4 [--int4_group 128] [--int4_scale_dtype float16|bfloat16|float32]
                  (the same weights as 4-bit words + group scales, W4A16: a quarter of the bytes)
+    python prepare_weights.py <model_dir> <new_file_dir> --merge_lora <adapter_dir> [--lora_scale 1.0]
+                 (the fp16 checkpoint with a LoRA adapter merged in: what --lora computes in HBM)
 """
 import argparse
 import sys
@@ -41,7 +43,29 @@ def main(argv=None):
                          "(0: one scale per output channel)")
     ap.add_argument("--int4_scale_dtype", choices=["float16", "bfloat16", "float32"], default="float16",
                     help="--quantize int4: dtype of the group scales")
+    ap.add_argument("--merge_lora", type=str, default=None, metavar="DIR",
+                    help="write bin_dir (per-layer files or an HF directory of safetensors files, fp16 / bf16 / "
+                         "fp32) with the LoRA adapter DIR merged into its weights, as fp16: the twin of a run with "
+                         "--lora DIR.  Runs on the GPU when there is one; otherwise by the numpy definition, layer "
+                         "by layer, which is slow for large models")
+    ap.add_argument("--lora_scale", type=float, default=None, help="--merge_lora: multiplies alpha / r (default 1.0)")
     a = ap.parse_args(argv)
+    if a.lora_scale is not None and not a.merge_lora:
+        ap.error("--lora_scale needs --merge_lora")
+    if a.merge_lora:
+        if a.quantize:
+            ap.error("--quantize does not combine with --merge_lora (the merged weights are fp16; quantise them "
+                     "in a second step)")
+        if a.synthetic:
+            ap.error("--synthetic does not combine with --merge_lora (write the checkpoint first)")
+        import torch
+        from flexible_llm_sharding_amd import lora
+        from flexible_llm_sharding_amd.config import ModelConfig
+        adapter = lora.LoraAdapter.load(ModelConfig.from_pretrained(a.bin_dir), a.merge_lora,
+                                        1.0 if a.lora_scale is None else a.lora_scale)
+        device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+        lora.write_twin(a.bin_dir, adapter, a.new_file_dir, merge=lora.ops_merge(device))
+        return 0
     if a.synthetic:
         import torch
         from flexible_llm_sharding_amd.config import preset
