@@ -232,6 +232,26 @@ int fls_dequant_int4_launches(uint64_t n, uint64_t group, int scale_es);
 int fls_dequant_int4_tail(void);
 // launch j of that chain: out[6] = {a, b, packed offset, scale offset, first group, groups} (host only)
 int fls_dequant_int4_segment(uint64_t n, uint64_t group, int scale_es, int j, uint64_t* out);
+// bitsandbytes 4-bit (NF4 / FP4) expansion in place (csrc/kernels/dequant.hip;
+// flexible_llm_sharding_amd/nf4.py holds the definition and the landing layout, region_layout()).
+// region: the tensor's 2n-byte image region (2-byte aligned) in which the n / 2 packed bytes (high
+// nibble first) and the n / block raw absmax entries (absmax_kind 0: fp32, 1: U8, double quantisation)
+// have landed segment by segment; afterwards it holds n fp16 values,
+//   w16[i] = fp16_rne(fp32_mul(code[nibble(i)], s_k)),  k = i / block,
+//   s_k = absmax[k]  (kind 0),  fp32_add(fp32_mul(code2[absmax[k]], nested_absmax[k / nested_block]), offset)  (kind 1)
+// every operation rounded on its own.  code: 16 floats, code2: 256 floats, nested_absmax:
+// ceil(n / block / nested_block) floats, all device memory the kernel only reads (kind 0 ignores the
+// last four arguments before s).  Uses no other device memory: fls_dequant_nf4_launches(n, block,
+// absmax_es) stream-ordered launches on s, the last a single block of at most fls_dequant_nf4_tail()
+// weights.  hipErrorInvalidValue, with nothing launched, for a missing pointer, an odd region
+// address, block % 32 != 0, n % block != 0, an unknown absmax kind, or kind 1 without its nested
+// tables / with nested_block 0; n == 0 returns 0.
+int fls_dequant_nf4(void* region, uint64_t n, uint64_t block, int absmax_kind, const float* code, const float* code2,
+                    const float* nested_absmax, uint64_t nested_block, float offset, fls_stream_t s);
+int fls_dequant_nf4_launches(uint64_t n, uint64_t block, int absmax_es);
+int fls_dequant_nf4_tail(void);
+// launch j of that chain: out[6] = {a, b, packed offset, absmax offset, first block, blocks} (host only)
+int fls_dequant_nf4_segment(uint64_t n, uint64_t block, int absmax_es, int j, uint64_t* out);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0
 int fls_gemv_skinny(const void* x, const void* w, void* c, int M, int N, int K, int ldx, int ldw, int ldc,
                     fls_stream_t s);

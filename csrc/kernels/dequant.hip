@@ -366,3 +366,179 @@ extern "C" int fls_dequant_int4(void* region, uint64_t n, uint64_t group, int sc
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// bitsandbytes 4-bit (NF4 / FP4) expansion in place (flexible_llm_sharding_amd/nf4.py holds the
+// definition; the landing layout is INT4's above with blocks for groups and raw absmax entries of 1
+// (U8, double quantisation) or 4 (fp32) bytes for scales).
+//
+//   w16[i] = fp16_rne( code[nibble(i)] * s_k ),  k = i / block
+//   s_k    = absmax[k]                                             (fp32 absmax)
+//   s_k    = code2[absmax_u8[k]] * nested_absmax[k / B2] + offset    (U8 absmax; multiply, round, add, round)
+//
+// Byte j of the packed stream holds element 2j in its HIGH nibble.  Each thread expands 32 weights of
+// one block (block % 32 == 0): one 16-byte load, its block's s_k once, 32 lookups in the 16-entry code
+// book, 32 plain fp32 multiplies, v_cvt_f16_f32, four 16-byte stores.  The code book sits in LDS:
+// its 16 dwords lie in 16 different banks and lanes that read the same entry are served by one
+// broadcast, so a ds_read_b32 with any mix of nibbles is conflict-free.  code2 (1 KB), nested_absmax
+// and the code book's source live in the table arena of the weight source and are only read.
+namespace {
+
+constexpr int kAbsmaxF32 = 0, kAbsmaxU8 = 1;
+
+// fp32 multiply, then fp32 add, each rounded: the product passes through an opaque register so that
+// -ffp-contract=fast cannot fuse the two into an FMA
+__device__ __forceinline__ float mul_then_add(float x, float y, float z) {
+  float p = x * y;
+  asm volatile("" : "+v"(p));
+  return p + z;
+}
+
+// s_k of block k whose raw absmax entry is entry idx of the entries at byte `off` of the region
+template <bool VEC, int KIND>
+__device__ __forceinline__ float block_scale(const uint8_t* region, uint64_t off, uint64_t idx, uint64_t k,
+                                             const float* __restrict__ code2, const float* __restrict__ nested,
+                                             uint64_t nested_block, float offset) {
+  if (KIND == kAbsmaxF32) return load_scale<VEC>(region, off, idx, 2);
+  const uint8_t q = region[off + idx];
+  return mul_then_add(code2[q], nested[k / nested_block], offset);
+}
+
+// this launch expands elements [a, a + cnt), cnt % 32 == 0; their packed bytes start at byte p_off.
+// Blocks [k0, k_next) have their absmax entries at s_off; block k_next (the one that straddles
+// a + cnt) at s_next.  TAIL: one block, cnt <= kTail4, every read completes before any write.
+template <bool VEC, bool TAIL, int KIND>
+__global__ __launch_bounds__(kThreads) void dequant_nf4_kernel(uint8_t* region, uint64_t a, uint64_t cnt,
+                                                               uint64_t p_off, uint64_t s_off, uint64_t k0,
+                                                               uint64_t k_next, uint64_t s_next, uint64_t block,
+                                                               const float* __restrict__ code,
+                                                               const float* __restrict__ code2,
+                                                               const float* __restrict__ nested,
+                                                               uint64_t nested_block, float offset) {
+  __shared__ float lut[16];
+  if (threadIdx.x < 16) lut[threadIdx.x] = code[threadIdx.x];
+  __syncthreads();
+  const uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  const uint64_t off = t * kPer4;
+  const bool active = off < cnt;
+  if (!TAIL && !active) return;
+  half_t o[kPer4];
+  if (active) {
+    uint32_t w[4];
+    const uint8_t* src = region + p_off + off / 2;
+    if (VEC) {
+      const uint4 v = *(const uint4*)src;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) |
+               ((uint32_t)src[4 * j + 3] << 24);
+    }
+    const uint64_t k = (a + off) / block;
+    const float s = k < k_next ? block_scale<VEC, KIND>(region, s_off, k - k0, k, code2, nested, nested_block, offset)
+                               : block_scale<VEC, KIND>(region, s_next, 0, k, code2, nested, nested_block, offset);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        // element b of word j: byte b / 2, an even b in the high nibble
+        const uint32_t u = (w[j] >> (4 * (b ^ 1))) & 15u;
+        o[8 * j + b] = to_half(lut[u] * s);
+      }
+  }
+  if (TAIL) __syncthreads();
+  if (!active) return;
+  half_t* dst = (half_t*)region + a + off;
+  if (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      half8 v;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) v[b] = o[8 * j + b];
+      *(half8*)(dst + 8 * j) = v;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kPer4; ++j) dst[j] = o[j];
+  }
+}
+
+inline bool argsn4_ok(uint64_t n, uint64_t block, int es) {
+  return block != 0 && block % 32 == 0 && n % block == 0 && (es == 1 || es == 4) && n < (1ull << 60);
+}
+
+template <bool VEC, bool TAIL>
+void launch_nf4(int kind, unsigned blocks, hipStream_t st, uint8_t* r, const Seg4& g, uint64_t s_next, uint64_t block,
+                const float* code, const float* code2, const float* nested, uint64_t nested_block, float offset) {
+  const uint64_t cnt = g.b - g.a, k_next = g.k0 + g.ng;
+  if (kind == kAbsmaxU8)
+    hipLaunchKernelGGL((dequant_nf4_kernel<VEC, TAIL, kAbsmaxU8>), dim3(blocks), dim3(kThreads), 0, st, r, g.a, cnt,
+                       g.p_off, g.s_off, g.k0, k_next, s_next, block, code, code2, nested, nested_block, offset);
+  else
+    hipLaunchKernelGGL((dequant_nf4_kernel<VEC, TAIL, kAbsmaxF32>), dim3(blocks), dim3(kThreads), 0, st, r, g.a, cnt,
+                       g.p_off, g.s_off, g.k0, k_next, s_next, block, code, code2, nested, nested_block, offset);
+}
+
+}  // namespace
+
+extern "C" int fls_dequant_nf4_tail(void) { return kTail4; }
+
+// launches fls_dequant_nf4 enqueues for a tensor of n weights in blocks of `block` with absmax
+// entries of absmax_es bytes (-1: bad arguments)
+extern "C" int fls_dequant_nf4_launches(uint64_t n, uint64_t block, int absmax_es) {
+  if (!argsn4_ok(n, block, absmax_es)) return -1;
+  if (n == 0) return 0;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, block, (uint64_t)absmax_es, segs);
+  return c > 0 ? c : -1;
+}
+
+// launch j (0 .. launches - 1) of that chain, for tests of the mirror: out = {a, b, packed offset,
+// absmax offset, first block, blocks}.  0, or -1 for bad arguments or j
+extern "C" int fls_dequant_nf4_segment(uint64_t n, uint64_t block, int absmax_es, int j, uint64_t* out) {
+  if (!out || n == 0 || !argsn4_ok(n, block, absmax_es)) return -1;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, block, (uint64_t)absmax_es, segs);
+  if (c <= 0 || j < 0 || j >= c) return -1;
+  const Seg4& s = segs[c - 1 - j];
+  out[0] = s.a; out[1] = s.b; out[2] = s.p_off; out[3] = s.s_off; out[4] = s.k0; out[5] = s.ng;
+  return 0;
+}
+
+extern "C" int fls_dequant_nf4(void* region, uint64_t n, uint64_t block, int absmax_kind, const float* code,
+                               const float* code2, const float* nested_absmax, uint64_t nested_block, float offset,
+                               fls_stream_t s) {
+  if (n == 0) return 0;
+  if (!region || ((uintptr_t)region & 1) || !code || ((uintptr_t)code & 3)) return (int)hipErrorInvalidValue;
+  if (absmax_kind != kAbsmaxF32 && absmax_kind != kAbsmaxU8) return (int)hipErrorInvalidValue;
+  if (absmax_kind == kAbsmaxU8 && (!code2 || !nested_absmax || nested_block == 0 || ((uintptr_t)code2 & 3) ||
+                                   ((uintptr_t)nested_absmax & 3)))
+    return (int)hipErrorInvalidValue;
+  const int es = absmax_kind == kAbsmaxU8 ? 1 : 4;
+  if (!argsn4_ok(n, block, es)) return (int)hipErrorInvalidValue;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, block, (uint64_t)es, segs);
+  if (c <= 0) return (int)hipErrorInvalidValue;
+  const bool vec = ((uintptr_t)region & 15) == 0;
+  auto st = (hipStream_t)s;
+  auto* r = (uint8_t*)region;
+  for (int j = c - 1; j >= 0; --j) {      // launch order: from the bottom segment to the tail
+    const Seg4& g4 = segs[j];
+    // the straddling block g4.b / block: the first entry of the next segment (towards the tail) that has any
+    uint64_t s_next = 0;
+    for (int i = j - 1; i >= 0; --i)
+      if (segs[i].ng) { s_next = segs[i].s_off; break; }
+    const uint64_t blocks = ((g4.b - g4.a) / kPer4 + kThreads - 1) / kThreads;
+    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    if (j == 0) {      // at most kTail4 weights: one block
+      if (vec) launch_nf4<true, true>(absmax_kind, 1u, st, r, g4, s_next, block, code, code2, nested_absmax, nested_block, offset);
+      else launch_nf4<false, true>(absmax_kind, 1u, st, r, g4, s_next, block, code, code2, nested_absmax, nested_block, offset);
+    } else {
+      if (vec) launch_nf4<true, false>(absmax_kind, (unsigned)blocks, st, r, g4, s_next, block, code, code2, nested_absmax, nested_block, offset);
+      else launch_nf4<false, false>(absmax_kind, (unsigned)blocks, st, r, g4, s_next, block, code, code2, nested_absmax, nested_block, offset);
+    }
+    FLS_CHECK_LAUNCH();
+  }
+  return 0;
+}

@@ -65,7 +65,7 @@ class Piece(ctypes.Structure):
                 ("kind", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
-KERNELS_ABI = 41  # bumped whenever a C signature in csrc/include/fls.h (or an accepted argument) changes
+KERNELS_ABI = 42  # bumped whenever a C signature in csrc/include/fls.h (or an accepted argument) changes
 
 
 def _load_kernels(path: str = _KERNELS):
@@ -142,6 +142,11 @@ def _load_kernels(path: str = _KERNELS):
     _bind(lib, "fls_dequant_int4_launches", c_int, c_uint64, c_uint64, c_int)
     _bind(lib, "fls_dequant_int4_tail", c_int)
     _bind(lib, "fls_dequant_int4_segment", c_int, c_uint64, c_uint64, c_int, c_int, c_void_p)
+    _bind(lib, "fls_dequant_nf4", c_int, c_void_p, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_uint64,
+          c_float, c_void_p)
+    _bind(lib, "fls_dequant_nf4_launches", c_int, c_uint64, c_uint64, c_int)
+    _bind(lib, "fls_dequant_nf4_tail", c_int)
+    _bind(lib, "fls_dequant_nf4_segment", c_int, c_uint64, c_uint64, c_int, c_int, c_void_p)
     _bind(lib, "fls_gemv_skinny", c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
           c_void_p)
     _bind(lib, "fls_lora_merge", c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_int,

@@ -65,8 +65,8 @@ def resolve_weight_cache(args, cfg: ModelConfig, comm: Comm, names: Sequence[str
     if mode in ("disk", "stream"):
         return "stream"
     need = 0
-    if source is not None and not sliced and (source.fp8_tensors() or source.int4_tensors()):
-        # an FP8 or INT4 checkpoint is pinned as its file bytes (runtime.weights.CompactHostStore), not
+    if source is not None and not sliced and (source.fp8_tensors() or source.int4_tensors() or source.nf4_tensors()):
+        # an FP8, INT4 or NF4 checkpoint is pinned as its file bytes (runtime.weights.CompactHostStore), not
         # as the fp16 image: a 70B FP8 model asks for about 70 GB instead of 138 GB, an INT4 one for 35 GB
         need = source.file_bytes(names)
         names = ()
@@ -117,9 +117,12 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device, lora=
     n_int4 = src.int4_tensors()
     if n_int4 and getattr(args, "verbose", False):
         print(f"INT4 checkpoint: {n_int4} W4A16 tensors are expanded to fp16 in HBM (weight-only INT4)", file=sys.stderr)
+    n_nf4 = src.nf4_tensors()
+    if n_nf4 and getattr(args, "verbose", False):
+        print(f"NF4 checkpoint: {n_nf4} bitsandbytes 4-bit tensors are expanded to fp16 in HBM", file=sys.stderr)
     if resolve_weight_cache(args, cfg, comm, mine, sliced=False, source=src) == "stream":
         return src
-    if n_fp8 or n_int4:
+    if n_fp8 or n_int4 or n_nf4:
         # the files' bytes pinned as they are, FP8 as FP8; norms are folded as each layer lands
         from .runtime.weights import CompactHostStore
         return CompactHostStore(src, pinned=device.type == "cuda")
@@ -138,6 +141,9 @@ def check_fp8_dp_shard(args, cfg: ModelConfig) -> None:
         return
     names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
     src = FileLayerSource(cfg, args.model_path, names=names)
+    if src.nf4_tensors():
+        raise ValueError("--dp_weight_shard true does not serve an NF4 checkpoint (its 1/G byte slices cut through "
+                         "tensors): pass --dp_weight_shard false, or run model parallel")
     if src.int4_tensors():
         raise ValueError("--dp_weight_shard true does not serve an INT4 checkpoint (its 1/G byte slices cut through "
                          "tensors): pass --dp_weight_shard false, or run model parallel")
@@ -693,6 +699,7 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
                                        else getattr(src, "total_bytes", 0))
     metrics["fp8_tensors"] = int(files.fp8_tensors()) if hasattr(files, "fp8_tensors") else 0
     metrics["int4_tensors"] = int(files.int4_tensors()) if hasattr(files, "int4_tensors") else 0
+    metrics["nf4_tensors"] = int(files.nf4_tensors()) if hasattr(files, "nf4_tensors") else 0
     ad = getattr(runner, "lora", None)
     metrics.update({"lora_tensors": int(ad.n_tensors) if ad else 0, "lora_rank_max": int(ad.rank_max) if ad else 0,
                     "lora_bytes": int(ad.nbytes) if ad else 0, "lora_merge_launches": int(ad.merge_launches) if ad else 0})

@@ -288,6 +288,11 @@ def region_layout(n: int, g: int, scale_es: int) -> Tuple[Segment, ...]:
     from the top of the ``2n``-byte region: the tail first, then each earlier launch as large as
     ``2 b <= scale_off`` allows.  The host code of ``fls_dequant_int4`` mirrors this function."""
     _check(n, g, scale_es)
+    return _segments(n, g, scale_es)
+
+
+def _segments(n: int, g: int, scale_es: int) -> Tuple[Segment, ...]:
+    """:func:`region_layout` for any scale size (nf4.py shares it for 1- and 4-byte block scales)."""
     segs: List[Segment] = []
     if n == 0:
         return ()
@@ -306,7 +311,7 @@ def region_layout(n: int, g: int, scale_es: int) -> Tuple[Segment, ...]:
         avail = top - 2 * b
         cnt = (avail - scale_es - 15) * 2 * g // (g + 2 * scale_es) // PER_THREAD * PER_THREAD
         if cnt <= 0:
-            raise AssertionError("INT4 landing layout made no progress")
+            raise AssertionError("4-bit landing layout made no progress")
         a = max(0, b - cnt)
     return tuple(reversed(segs))
 

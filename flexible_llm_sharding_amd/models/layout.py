@@ -283,18 +283,26 @@ def check_layer_tensors(cfg: ModelConfig, layer_name: str, available) -> None:
         return
     from ..fp8 import is_scale_name, weight_of_scale
     from ..int4 import is_companion_name, weight_of_companion
+    from .. import nf4
     want = {pl.hf_name for pl in placements(cfg, layer_name)}
     # (the scale tensors of an FP8 checkpoint follow their weight: fp8.py; so do the words, scales
-    # and shape of an INT4 weight: int4.py)
+    # and shape of an INT4 weight: int4.py; and the absmax, code books and quant state of a
+    # bitsandbytes 4-bit weight: nf4.py)
     extra = sorted(k for k in available if k not in want and not k.endswith("rotary_emb.inv_freq")
                    and not (is_scale_name(k) and weight_of_scale(k) in want)
-                   and not (is_companion_name(k) and weight_of_companion(k) in want))
+                   and not (is_companion_name(k) and weight_of_companion(k) in want)
+                   and not (nf4.is_companion_name(k) and nf4.weight_of_companion(k) in want))
     if extra:
         raise NotImplementedError(f"model_type={cfg.model_type!r} runs as Llama, but {layer_name} holds tensors a "
                                   f"Llama layer does not have: {extra[:4]}")
 
 
 # ------------------------------------------------------------------- packing
+def _is_nf4(key: str, sd) -> bool:
+    from ..nf4 import is_nf4_source
+    return is_nf4_source(key, sd)
+
+
 def hf_param_names(cfg: ModelConfig, layer_name: str) -> List[str]:
     return [pl.hf_name for pl in placements(cfg, layer_name)]
 
@@ -322,6 +330,9 @@ def pack_layer(cfg: ModelConfig, layer_name: str, sd: Dict[str, torch.Tensor],
         if key != pl.hf_name and key == pl.hf_name + "_packed":
             from .. import int4             # weight-only INT4: the image holds w16 (int4.py)
             t = int4.dequantize_entry(sd, pl.hf_name, pl.shape, f"{layer_name}: ")
+        elif key == pl.hf_name and _is_nf4(key, sd):
+            from .. import nf4              # bitsandbytes 4-bit: the image holds w16 (nf4.py)
+            t = nf4.dequantize_entry(sd, pl.hf_name, pl.shape, f"{layer_name}: ")
         else:
             t = sd[key]
         if tuple(t.shape) != pl.shape:

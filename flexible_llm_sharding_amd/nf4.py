@@ -1,0 +1,417 @@
+"""bitsandbytes 4-bit (NF4 / FP4) checkpoints: the host definition.
+
+A 2-D projection weight ``X.weight`` of model shape ``[out, in]`` with ``N = out * in`` is stored as
+
+    X.weight                      U8  [N / 2, 1] (or [N / 2])   byte j holds flat row-major element 2j
+                                                                in its HIGH nibble, 2j + 1 in its low one
+    X.weight.quant_map            F32 [16]                      the code book ``code``
+    X.weight.absmax               F32 [N / B], or U8 [N / B] with double quantisation: one entry per
+                                                                block of B consecutive flat elements
+    X.weight.nested_absmax        F32 [ceil((N / B) / B2)]      double quantisation only
+    X.weight.nested_quant_map     F32 [256]                     double quantisation only: ``code2``
+    X.weight.quant_state.bitsandbytes__nf4 (or ``__fp4``)
+                                  U8  [len]                     UTF-8 JSON: quant_type, blocksize (B),
+                                                                dtype, shape ([out, in]); with double
+                                                                quantisation also nested_blocksize (B2),
+                                                                nested_dtype, nested_offset
+
+``B`` is a multiple of 32 that divides ``N``; blocks run over the flat tensor and may straddle rows.
+``B2 >= 1``; the last nested block may be partial.  With ``u_i`` the nibble of flat element ``i`` and
+``k = i // B`` the value is
+
+    s_k    = absmax[k]                                                                (F32 absmax)
+    s_k    = fp32_add(fp32_mul(code2[absmax_u8[k]], nested_absmax[k // B2]), fp32(nested_offset))
+    w16[i] = fp16_rne(fp32_mul(code[u_i], s_k))
+
+every operation a separately rounded fp32 operation (no fused multiply-add); overflow goes to +-inf
+and ``0 * negative`` is -0.  The code book is always the file's: ``nf4``, ``fp4`` or any other 16
+floats load the same way.  The ``dtype`` field of the quant state is ignored (for a ``bfloat16``
+state bitsandbytes itself rounds to bf16; here the same fp32 product is rounded to fp16).  This is
+the layout ``save_pretrained`` of a ``load_in_4bit`` model is understood to write.
+
+The *fp16 twin* (:func:`write_twin`) is the same directory with ``X.weight`` written as ``w16`` and
+the companions removed: a run on the NF4 checkpoint gives, bit for bit, the outputs of the same run
+on its twin.
+
+Landing layout (:func:`region_layout`): as INT4's (``int4.region_layout``, whose docstring has the
+argument), segment by segment stacked down from the top of the tensor's own ``2N``-byte region.  A
+segment holds the packed bytes of its elements and the *raw absmax bytes* (1 or 4 each) of the blocks
+that end in it, at a 16-byte aligned offset.  The small tables (``code``, ``code2``,
+``nested_absmax``, the offset) do not travel with the weights: they are read at plan time and live
+on the device in the source's table arena.
+"""
+from __future__ import annotations
+
+import functools
+import glob
+import json
+import math
+import os
+import shutil
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from . import int4
+from .fp8 import is_quantized_name
+from .int4 import Segment
+
+PER_THREAD = int4.PER_THREAD       # weights per kernel thread: one 16-byte load of nibbles
+TAIL = int4.TAIL                   # weights the final single-block launch can hold
+ABSMAX_F32, ABSMAX_U8 = 0, 1       # fls_dequant_nf4's absmax_kind
+QUANT_TYPES = ("nf4", "fp4")
+STATE = ".quant_state.bitsandbytes__"
+ABSMAX, QUANT_MAP, NESTED_ABSMAX, NESTED_QUANT_MAP = ".absmax", ".quant_map", ".nested_absmax", ".nested_quant_map"
+NESTED_BLOCK = 256                 # the writer's nested block size
+# the published NF4 code book (QLoRA, Dettmers et al. 2023, appendix E)
+NF4_CODE = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
+            -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
+            0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+            0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0)
+
+
+class QuantState(NamedTuple):
+    """The checked quant state of one weight: what :func:`dequantize` needs besides the packed bytes
+    and the absmax tensor (whose name is ``absmax_name``)."""
+    quant_type: str
+    block: int
+    absmax_kind: int
+    code: torch.Tensor                        # fp32 [16]
+    code2: Optional[torch.Tensor]             # fp32 [256] (U8 absmax)
+    nested_absmax: Optional[torch.Tensor]     # fp32 [ceil(N / B / B2)] (U8 absmax)
+    nested_block: int
+    offset: float
+    absmax_name: str
+    state_name: str
+
+    @property
+    def absmax_es(self) -> int:
+        return 1 if self.absmax_kind == ABSMAX_U8 else 4
+
+
+# ------------------------------------------------------------------------------- the value
+def block_scales(absmax: torch.Tensor, code2: Optional[torch.Tensor] = None,
+                 nested_absmax: Optional[torch.Tensor] = None, nested_block: int = 0,
+                 offset: float = 0.0) -> torch.Tensor:
+    """``s_k`` (fp32) of every block from the absmax tensor as stored (F32, or U8 with the nested tables)."""
+    a = absmax.detach().to("cpu").reshape(-1)
+    if a.dtype == torch.float32:
+        return a.contiguous()
+    if a.dtype != torch.uint8:
+        raise TypeError(f"absmax is F32 or U8, got {a.dtype}")
+    if code2 is None or nested_absmax is None or nested_block < 1:
+        raise ValueError("a U8 absmax needs code2, nested_absmax and a nested block size")
+    k = torch.arange(a.numel(), dtype=torch.int64)
+    c2 = code2.detach().to("cpu").to(torch.float32).reshape(-1)[a.to(torch.int64)]
+    nb = nested_absmax.detach().to("cpu").to(torch.float32).reshape(-1)[k // int(nested_block)]
+    prod = c2 * nb                                               # one rounding
+    return prod + torch.tensor(float(offset), dtype=torch.float32)      # another
+
+
+def dequantize(packed: torch.Tensor, code: torch.Tensor, absmax: torch.Tensor, shape: Sequence[int], block: int,
+               code2: Optional[torch.Tensor] = None, nested_absmax: Optional[torch.Tensor] = None,
+               nested_block: int = 0, offset: float = 0.0) -> torch.Tensor:
+    """``w16`` of shape ``shape`` from the packed bytes (``N / 2``, any shape), the 16-entry code book
+    and the absmax tensor as stored."""
+    n = int(math.prod(int(x) for x in shape))
+    block = int(block)
+    by = packed.detach().to("cpu").reshape(-1)
+    if by.dtype != torch.uint8 or by.numel() * 2 != n:
+        raise ValueError(f"the packed bytes of {n} weights are {n // 2} U8, got {by.dtype} [{by.numel()}]")
+    if block <= 0 or block % 32 or n % block:
+        raise ValueError(f"blocksize {block} is no multiple of 32 that divides the {n} weights")
+    if absmax.numel() != n // block:
+        raise ValueError(f"absmax has {absmax.numel()} entries, {n} weights in blocks of {block} have {n // block}")
+    c = code.detach().to("cpu").to(torch.float32).reshape(-1)
+    if c.numel() != 16:
+        raise ValueError(f"the code book has 16 entries, got {c.numel()}")
+    s = block_scales(absmax, code2, nested_absmax, nested_block, offset)
+    u = torch.stack((by >> 4, by & 15), -1).reshape(n // block, block).to(torch.int64)
+    return (c[u] * s.reshape(-1, 1)).to(torch.float16).reshape(tuple(int(x) for x in shape))
+
+
+# --------------------------------------------------------------------------- names
+def _suffix_start(name: str) -> int:
+    """Index where the companion suffix of ``name`` starts (after ``X.weight``), or -1."""
+    for suf in (ABSMAX, QUANT_MAP, NESTED_ABSMAX, NESTED_QUANT_MAP):
+        if name.endswith(".weight" + suf):
+            return len(name) - len(suf)
+    i = name.rfind(".weight" + STATE)
+    return i + len(".weight") if i >= 0 else -1
+
+
+def is_companion_name(name: str) -> bool:
+    """A tensor that belongs to a bitsandbytes 4-bit weight: absmax, a code book, a nested table or
+    the quant state."""
+    return _suffix_start(name) >= 0
+
+
+def weight_of_companion(name: str) -> str:
+    """``X.weight`` for ``X.weight.absmax`` / ``.quant_map`` / ... / ``.quant_state.bitsandbytes__nf4``."""
+    i = _suffix_start(name)
+    if i < 0:
+        raise ValueError(name)
+    return name[:i]
+
+
+def state_name(weight_name: str, available) -> Optional[str]:
+    """The quant-state tensor of ``weight_name`` among ``available``, or None."""
+    pre = weight_name + STATE
+    for k in available:
+        if k.startswith(pre):
+            return k
+    return None
+
+
+def is_nf4_source(weight_name: str, infos) -> bool:
+    """``weight_name`` is a U8 tensor with a bitsandbytes quant state next to it."""
+    return (weight_name in infos and infos[weight_name].dtype == torch.uint8
+            and state_name(weight_name, infos) is not None)
+
+
+def check_entry(weight_name: str, infos, shape: Sequence[int], read: Callable[[str], torch.Tensor],
+                where: str = "") -> QuantState:
+    """Parse and validate the quant state and every companion of 4-bit weight ``weight_name`` whose
+    placement has ``shape``.  ``infos`` maps names to objects with ``dtype`` and ``shape`` (tensors,
+    or safetensors header entries); ``read(name)`` gives a small companion's contents (the absmax
+    tensor is not read).  TypeError naming the tensor otherwise."""
+    what = f"{where}{weight_name} (NF4)"
+    sn = state_name(weight_name, infos)
+    if sn is None:
+        raise TypeError(f"{what} has no quant state ({weight_name}{STATE}nf4 / fp4)")
+    if len(tuple(shape)) != 2:
+        raise TypeError(f"{what}: only 2-D projection weights may be 4-bit, this one has shape {tuple(shape)}")
+    out, inn = (int(x) for x in shape)
+    n = out * inn
+    st = infos[sn]
+    if st.dtype != torch.uint8 or len(tuple(st.shape)) != 1:
+        raise TypeError(f"{what}: {sn} is {st.dtype} {tuple(st.shape)}, not U8 [len] (UTF-8 JSON)")
+    try:
+        js = json.loads(bytes(read(sn).reshape(-1).tolist()).decode("utf-8"))
+        if not isinstance(js, dict):
+            raise ValueError("not an object")
+    except (ValueError, UnicodeDecodeError) as e:
+        raise TypeError(f"{what}: {sn} does not parse as JSON ({e})") from None
+    for f in ("quant_type", "blocksize", "shape"):
+        if f not in js:
+            raise TypeError(f"{what}: {sn} lacks the field {f!r}")
+    qt = js["quant_type"]
+    if qt not in QUANT_TYPES or not sn.endswith("__" + str(qt)):
+        raise TypeError(f"{what}: quant_type {qt!r} of {sn}; nf4 and fp4 are supported")
+    try:
+        jshape = tuple(int(x) for x in js["shape"])
+        block = int(js["blocksize"])
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: {sn} has a shape / blocksize that is no integer") from None
+    if jshape != (out, inn):
+        raise TypeError(f"{what}: the quant state's shape is {list(jshape)}, the model expects {[out, inn]}")
+    p = infos[weight_name]
+    if p.dtype != torch.uint8 or n % 2 or tuple(p.shape) not in ((n // 2, 1), (n // 2,)):
+        raise TypeError(f"{what}: packed as {p.dtype} {tuple(p.shape)}, a [{out}, {inn}] weight packs to U8 "
+                        f"[{n // 2}, 1] (two weights per byte)")
+    if block <= 0 or block % 32 or n % block:
+        raise TypeError(f"{what}: blocksize {block} is no multiple of 32 that divides the {n} weights")
+
+    def table(suffix: str, count: int, why: str = "") -> torch.Tensor:
+        k = weight_name + suffix
+        if k not in infos:
+            raise TypeError(f"{what} has no {k}{why}")
+        ti = infos[k]
+        if ti.dtype != torch.float32 or tuple(ti.shape) != (count,):
+            raise TypeError(f"{what}: {k} is {ti.dtype} {tuple(ti.shape)}, not F32 [{count}]")
+        t = read(k).detach().to("cpu").reshape(-1).to(torch.float32).contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise TypeError(f"{what}: {k} holds a value that is not finite")
+        return t
+
+    code = table(QUANT_MAP, 16)
+    ak = weight_name + ABSMAX
+    if ak not in infos:
+        raise TypeError(f"{what} has no {ak}")
+    ai = infos[ak]
+    if ai.dtype not in (torch.float32, torch.uint8) or tuple(ai.shape) != (n // block,):
+        raise TypeError(f"{what}: {ak} is {ai.dtype} {tuple(ai.shape)}, not F32 or U8 [{n // block}] (one entry per "
+                        f"block of {block})")
+    if ai.dtype == torch.float32:
+        return QuantState(qt, block, ABSMAX_F32, code, None, None, 0, 0.0, ak, sn)
+    why = f" (its {ak} is U8: double quantisation)"
+    for f in ("nested_blocksize", "nested_offset"):
+        if f not in js:
+            raise TypeError(f"{what}: {sn} lacks the field {f!r}{why}")
+    try:
+        b2, off = int(js["nested_blocksize"]), float(js["nested_offset"])
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: {sn} has a nested_blocksize / nested_offset that is no number") from None
+    if b2 < 1:
+        raise TypeError(f"{what}: nested_blocksize {b2} is not positive")
+    if not math.isfinite(off) or not math.isfinite(float(torch.tensor(off, dtype=torch.float32))):
+        raise TypeError(f"{what}: nested_offset {off} is not finite")
+    nested = table(NESTED_ABSMAX, -(-(n // block) // b2), why)
+    code2 = table(NESTED_QUANT_MAP, 256, why)
+    return QuantState(qt, block, ABSMAX_U8, code, code2, nested, b2, off, ak, sn)
+
+
+def dequantize_entry(sd: Dict[str, torch.Tensor], weight_name: str, shape: Sequence[int], where: str = "") -> torch.Tensor:
+    """``w16`` of 4-bit weight ``weight_name`` of a state dict, validated against ``shape``."""
+    qs = check_entry(weight_name, sd, shape, sd.__getitem__, where)
+    return dequantize(sd[weight_name], qs.code, sd[qs.absmax_name], shape, qs.block, qs.code2, qs.nested_absmax,
+                      qs.nested_block, qs.offset)
+
+
+# --------------------------------------------------------------------------- converter
+def writer_code2() -> torch.Tensor:
+    """The writer's own ``code2``: 256 sorted fp32 values, -1 ... 0 in steps of 1/128 (entries 0 ..
+    128), then up to 1 in steps of 1/127 (entries 128 .. 255).  It holds -1, 0 and 1."""
+    i = torch.arange(256, dtype=torch.float64)
+    return torch.where(i <= 128, (i - 128) / 128, (i - 128) / 127).to(torch.float32)
+
+
+def _nearest(x: torch.Tensor, code: torch.Tensor) -> torch.Tensor:
+    """Index of the entry of the sorted ``code`` nearest to each ``x`` (ties to the lower index):
+    ``x`` against the midpoints of neighbouring entries, both in fp64."""
+    c = code.to(torch.float64)
+    mid = ((c[:-1] + c[1:]) / 2).contiguous()
+    return torch.bucketize(x.to(torch.float64), mid, right=False)       # mid[i-1] < x <= mid[i]  ->  i
+
+
+def quantize(w: torch.Tensor, block: int = 64, double_quant: bool = True,
+             code: Sequence[float] = NF4_CODE, quant_type: str = "nf4") -> Dict[str, torch.Tensor]:
+    """The tensors of ``w`` ([out, in]) in the stored form, keyed by suffix after ``X.weight`` (``""``
+    is the packed tensor).  ``absmax`` is each block's largest magnitude, 1 for an all-zero block;
+    each weight takes the nearest entry of ``code`` to ``fp32(w) / absmax``, ties to the lower index.
+    ``double_quant``: ``nested_offset`` is the mean of the absmax values, the nested blocks hold
+    ``NESTED_BLOCK`` of ``absmax - offset``, each scaled by its largest magnitude (1 if zero) to the
+    nearest entry of :func:`writer_code2`."""
+    if w.dim() != 2:
+        raise ValueError(f"4-bit weights are 2-D, got shape {tuple(w.shape)}")
+    n, block = w.numel(), int(block)
+    if block <= 0 or block % 32 or n % block:
+        raise ValueError(f"--nf4_block {block}: a multiple of 32 that divides the {n} weights of a tensor")
+    c = torch.tensor(list(code), dtype=torch.float32)
+    if c.numel() != 16 or bool((c[1:] < c[:-1]).any()):
+        raise ValueError("the code book is 16 sorted values")
+    f = w.detach().to("cpu").to(torch.float32).reshape(n // block, block)
+    absmax = f.abs().amax(-1)
+    absmax = torch.where(absmax == 0, torch.ones_like(absmax), absmax)
+    by = torch.empty(n // 2, dtype=torch.uint8)
+    rows = max(1, (1 << 22) // block)                     # (bounded temporaries for 70B-sized tensors)
+    for r0 in range(0, n // block, rows):
+        u = _nearest(f[r0:r0 + rows] / absmax[r0:r0 + rows, None], c).to(torch.uint8).reshape(-1, 2)
+        by[r0 * block // 2:r0 * block // 2 + u.shape[0]] = (u[:, 0] << 4) | u[:, 1]
+    state = {"quant_type": quant_type, "blocksize": block, "dtype": str(w.dtype).replace("torch.", ""),
+             "shape": [int(x) for x in w.shape]}
+    out = {"": by.reshape(-1, 1), QUANT_MAP: c}
+    if not double_quant:
+        out[ABSMAX] = absmax.contiguous()
+    else:
+        offset = float(absmax.mean())
+        resid = absmax - torch.tensor(offset, dtype=torch.float32)
+        nb = -(-resid.numel() // NESTED_BLOCK)
+        pad = torch.zeros(nb * NESTED_BLOCK, dtype=torch.float32)
+        pad[:resid.numel()] = resid
+        nested = pad.reshape(nb, NESTED_BLOCK).abs().amax(-1)
+        nested = torch.where(nested == 0, torch.ones_like(nested), nested)
+        code2 = writer_code2()
+        q = _nearest(pad.reshape(nb, NESTED_BLOCK) / nested[:, None], code2).to(torch.uint8)
+        out[ABSMAX] = q.reshape(-1)[:resid.numel()].contiguous()
+        out[NESTED_ABSMAX] = nested.contiguous()
+        out[NESTED_QUANT_MAP] = code2
+        state.update({"nested_blocksize": NESTED_BLOCK, "nested_dtype": "float32", "nested_offset": offset})
+    out[STATE + quant_type] = torch.tensor(list(json.dumps(state).encode("utf-8")), dtype=torch.uint8)
+    return out
+
+
+def quantize_state_dict(sd: Dict[str, torch.Tensor], block: int = 64, double_quant: bool = True) -> Dict[str, torch.Tensor]:
+    """``--quantize nf4`` of one file's tensors: every 2-D projection weight
+    (``fp8.is_quantized_name``) of a float dtype becomes the packed tensor and its companions;
+    everything else, the tensors of a checkpoint that is 4-bit already included, passes through."""
+    out = {}
+    for k, v in sd.items():
+        if is_quantized_name(k) and v.dim() == 2 and v.dtype in (torch.float16, torch.bfloat16, torch.float32):
+            for suf, t in quantize(v, block, double_quant).items():
+                out[k + suf] = t
+        else:
+            out[k] = v
+    return out
+
+
+def dequantize_state_dict(sd: Dict[str, torch.Tensor], where: str = "") -> Dict[str, torch.Tensor]:
+    """The twin of one file's tensors: ``X.weight`` = ``w16``, the companions dropped."""
+    out = {}
+    for k, v in sd.items():
+        if is_companion_name(k) and is_nf4_source(weight_of_companion(k), sd):
+            continue
+        if is_nf4_source(k, sd):
+            sn = state_name(k, sd)
+            try:
+                shape = tuple(int(x) for x in json.loads(bytes(sd[sn].reshape(-1).tolist()).decode("utf-8"))["shape"])
+            except (ValueError, UnicodeDecodeError, KeyError, TypeError):
+                raise TypeError(f"{where}{k} (NF4): {sn} does not give the weight's shape") from None
+            out[k] = dequantize_entry(sd, k, shape, where)
+        else:
+            out[k] = v
+    return out
+
+
+def write_twin(src_dir: str, dst_dir: str) -> None:
+    """Write the fp16 twin of the checkpoint directory ``src_dir`` to ``dst_dir``."""
+    from .utils.safetensors_io import load_file, save_file
+    os.makedirs(dst_dir, exist_ok=True)
+    for fn in sorted(glob.glob(os.path.join(src_dir, "*"))):
+        base = os.path.basename(fn)
+        if os.path.isdir(fn):
+            continue
+        if base.endswith(".safetensors"):
+            save_file(dequantize_state_dict(load_file(fn), base + ": "), os.path.join(dst_dir, base))
+        else:
+            shutil.copy(fn, os.path.join(dst_dir, base))
+
+
+# --------------------------------------------------------------------------- landing layout
+def _check(n: int, block: int, scale_es: int) -> None:
+    if scale_es not in (1, 4):
+        raise ValueError(f"absmax entries have 1 (U8) or 4 (F32) bytes, not {scale_es}")
+    if block <= 0 or block % 32 or n < 0 or n % block:
+        raise ValueError(f"NF4: blocksize {block} must be a multiple of 32 that divides the {n} weights")
+
+
+@functools.lru_cache(maxsize=256)
+def region_layout(n: int, block: int, scale_es: int) -> Tuple[Segment, ...]:
+    """The segments of a tensor of ``n`` weights in launch order: ``int4.region_layout``'s rule for
+    blocks of ``block`` weights whose raw absmax entries have ``scale_es`` bytes (``Segment``'s
+    groups are the blocks).  The host code of ``fls_dequant_nf4`` mirrors this function."""
+    _check(n, block, scale_es)
+    return int4._segments(n, block, scale_es)
+
+
+def schedule(n: int, block: int, scale_es: int) -> List[Tuple[int, int]]:
+    """The ``[a, b)`` element ranges of the launches of ``fls_dequant_nf4``, in order."""
+    return [(s.a, s.b) for s in region_layout(n, block, scale_es)]
+
+
+def landing_span(n: int, block: int, scale_es: int) -> Tuple[int, int]:
+    """``(offset, bytes)`` of the part of the region the landed inputs occupy."""
+    lay = region_layout(n, block, scale_es)
+    return (lay[0].scale_off, 2 * n - lay[0].scale_off) if lay else (0, 0)
+
+
+def land(region: torch.Tensor, packed_bytes: torch.Tensor, absmax_bytes: torch.Tensor, n: int, block: int,
+         scale_es: int) -> None:
+    """Place a tensor's packed bytes (``n / 2``) and raw absmax bytes into the uint8 ``region`` the
+    way the loader does (tests, benchmarks)."""
+    for s in region_layout(n, block, scale_es):
+        region[s.packed_off:s.packed_off + (s.b - s.a) // 2].copy_(packed_bytes[s.a // 2:s.b // 2])
+        if s.n_groups:
+            region[s.scale_off:s.scale_off + s.n_groups * scale_es].copy_(
+                absmax_bytes[s.first_group * scale_es:(s.first_group + s.n_groups) * scale_es])
+
+
+def unland(region: torch.Tensor, n: int, block: int, scale_es: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The inverse of :func:`land` on a CPU uint8 ``region``: ``(packed bytes, raw absmax bytes)``."""
+    packed = torch.empty(n // 2, dtype=torch.uint8)
+    absmax = torch.empty(n // block * scale_es, dtype=torch.uint8)
+    for s in region_layout(n, block, scale_es):
+        packed[s.a // 2:s.b // 2] = region[s.packed_off:s.packed_off + (s.b - s.a) // 2]
+        absmax[s.first_group * scale_es:(s.first_group + s.n_groups) * scale_es] = \
+            region[s.scale_off:s.scale_off + s.n_groups * scale_es]
+    return packed, absmax

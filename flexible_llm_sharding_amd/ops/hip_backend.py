@@ -734,6 +734,34 @@ class HipOps:
         _chk(self.k.fls_lora_merge(w.data_ptr(), w.shape[0], w.shape[1], a.data_ptr(), bs.data_ptr(), int(r),
                                    _stream()), "fls_lora_merge")
 
+    def dequant_nf4(self, region: torch.Tensor, numel: int, block: int, absmax_kind: int, code: torch.Tensor,
+                    code2: torch.Tensor = None, nested_absmax: torch.Tensor = None, nested_block: int = 0,
+                    offset: float = 0.0) -> None:
+        """Expand the bitsandbytes 4-bit tensor of ``numel`` weights that landed in its ``2 * numel``-byte
+        ``region`` (nf4.region_layout) to fp16 in place (nf4.py's definition; csrc/kernels/dequant.hip).
+        ``code`` (16), ``code2`` (256) and ``nested_absmax`` are fp32 tensors on the region's device."""
+        from ..nf4 import ABSMAX_F32, ABSMAX_U8
+        if region.numel() * region.element_size() != 2 * numel or not region.is_contiguous():
+            raise ValueError("the region of an NF4 tensor is 2 bytes per weight")
+        if absmax_kind not in (ABSMAX_F32, ABSMAX_U8):
+            raise ValueError(f"NF4 absmax kind {absmax_kind}: 0 (fp32) or 1 (U8)")
+        if block <= 0 or block % 32 or numel % block:
+            raise ValueError(f"NF4 blocksize {block} is no multiple of 32 that divides {numel} weights")
+        tables = [(code, 16)]
+        if absmax_kind == ABSMAX_U8:
+            if code2 is None or nested_absmax is None or nested_block < 1:
+                raise ValueError("a U8 absmax needs code2, nested_absmax and a nested block size")
+            tables += [(code2, 256), (nested_absmax, -(-(numel // block) // nested_block))]
+        for t, cnt in tables:
+            if t.dtype != torch.float32 or t.device != region.device or t.numel() != cnt or not t.is_contiguous():
+                raise ValueError(f"NF4 tables are contiguous fp32 on {region.device}, this one of {cnt} entries is "
+                                 f"{t.dtype} [{t.numel()}] on {t.device}")
+        u8 = absmax_kind == ABSMAX_U8
+        _chk(self.k.fls_dequant_nf4(region.data_ptr(), numel, block, absmax_kind, code.data_ptr(),
+                                    code2.data_ptr() if u8 else None, nested_absmax.data_ptr() if u8 else None,
+                                    nested_block if u8 else 0, float(offset) if u8 else 0.0, _stream()),
+             "fls_dequant_nf4")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -375,6 +375,22 @@ class TorchOps:
                             (rows, group))
         b.view(torch.float16).copy_(w.reshape(-1))
 
+    def dequant_nf4(self, region: torch.Tensor, numel: int, block: int, absmax_kind: int, code: torch.Tensor,
+                    code2=None, nested_absmax=None, nested_block: int = 0, offset: float = 0.0) -> None:
+        """The bitsandbytes 4-bit tensor of ``numel`` weights that landed in its ``2 * numel``-byte
+        ``region`` (nf4.region_layout) -> fp16 in place, by the host definition (nf4.dequantize)."""
+        from .. import nf4
+        b = region.view(torch.uint8)
+        if b.numel() != 2 * numel:
+            raise ValueError("the region of an NF4 tensor is 2 bytes per weight")
+        if numel == 0:
+            return
+        u8 = absmax_kind == nf4.ABSMAX_U8
+        packed, raw = nf4.unland(b.to("cpu"), numel, block, 1 if u8 else 4)
+        w = nf4.dequantize(packed, code, raw if u8 else raw.view(torch.float32), (numel // block, block), block,
+                           code2, nested_absmax, nested_block, offset)
+        b.view(torch.float16).copy_(w.reshape(-1))
+
     # ------------------------------------------------------- synthetic init
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         """Random-init one packed layer in place (norm weights ~ 1, embeddings ~ N(0,1))."""

@@ -26,7 +26,11 @@ Here the same small-RAM envelope costs no CPU work per pass:
 * INT4 tensors of a weight-only W4A16 checkpoint (:mod:`..int4`) are read and copied as they are,
   nibbles and raw group scales, segment by segment into the top of the tensor's own region of the
   image (``int4.region_layout``) and expanded to fp16 in place there by ``fls_dequant_int4`` on the
-  copy stream; the scales travel with the weights and take no device memory of their own.
+  copy stream; the scales travel with the weights and take no device memory of their own;
+* bitsandbytes 4-bit (NF4 / FP4) tensors (:mod:`..nf4`) land the same way, packed bytes and raw
+  absmax bytes segment by segment (``nf4.region_layout``), and are expanded by ``fls_dequant_nf4``;
+  their small tables (code books, nested absmax, offset) are read at plan time and live in the
+  source's device arena next to the FP8 scales.
 
 Data-parallel ranks stream only their 1/G byte range of the packed image
 (:meth:`LayerPlan.pieces`) and complete the layer with an RCCL all-gather
@@ -44,7 +48,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, fp8, int4, knobs
+from .. import _native, fp8, int4, knobs, nf4
 from ..config import ModelConfig
 from ..models.layout import check_layer_tensors, layer_kind, layer_layout, placements, source_key
 from ..utils.layer_format import layer_file
@@ -54,6 +58,7 @@ from .weights import LayerSource
 
 KIND_RAW, KIND_F32 = 0, 1
 _SRC_ES = {torch.float16: 2, torch.bfloat16: 2, torch.float32: 4, fp8.FP8_DTYPE: 1}
+_ABSMAX_DTYPE = {nf4.ABSMAX_F32: torch.float32, nf4.ABSMAX_U8: torch.uint8}
 
 
 @dataclass(frozen=True)
@@ -68,7 +73,12 @@ class TensorRun:
 
     An INT4 tensor (``group`` > 0, weight-only W4A16: :mod:`..int4`) is ``numel / 2`` bytes of
     nibbles at ``file_off`` plus ``numel / group`` raw scales of ``scale_dtype`` at ``scale_off`` of
-    the file; both land in the top of the region as ``int4.region_layout`` lays them out."""
+    the file; both land in the top of the region as ``int4.region_layout`` lays them out.
+
+    A bitsandbytes 4-bit tensor (``quant`` set: :mod:`..nf4`) is ``numel / 2`` packed bytes at
+    ``file_off`` plus ``numel / group`` raw absmax entries (``group`` is the block size; 1 or 4 bytes
+    each) at ``scale_off`` of the file, landing as ``nf4.region_layout`` lays them out; ``quant``
+    holds the checked quant state with the small tables (read at plan time)."""
     hf_name: str
     file_off: int
     img_off: int
@@ -80,6 +90,7 @@ class TensorRun:
     group: int = 0
     scale_off: int = 0
     scale_dtype: Optional[torch.dtype] = None
+    quant: Optional[nf4.QuantState] = field(default=None, compare=False, repr=False)
 
     @property
     def src_es(self) -> int:
@@ -87,18 +98,44 @@ class TensorRun:
 
     @property
     def is_int4(self) -> bool:
+        return self.group > 0 and self.quant is None
+
+    @property
+    def is_nf4(self) -> bool:
+        return self.quant is not None
+
+    @property
+    def lands_segmented(self) -> bool:
+        """A 4-bit tensor (INT4 or NF4): it lands segment by segment and loads whole."""
         return self.group > 0
 
     @property
     def scale_es(self) -> int:
-        return _SRC_ES[self.scale_dtype]
+        return self.quant.absmax_es if self.is_nf4 else _SRC_ES[self.scale_dtype]
 
     @property
     def file_nbytes(self) -> int:
         """Tensor bytes of the file that a pass reads and copies for this tensor."""
-        if self.is_int4:
+        if self.lands_segmented:
             return self.numel // 2 + self.numel // self.group * self.scale_es
         return self.numel * self.src_es
+
+    def nf4_pieces(self) -> List[Tuple[int, int, int]]:
+        """(file_off, bytes, region offset) of an NF4 tensor's landing pieces: per segment its packed
+        bytes and, where it holds any, the raw absmax bytes of the blocks that end in it."""
+        out = []
+        for s in nf4.region_layout(self.numel, self.group, self.scale_es):
+            if s.n_groups:
+                out.append((self.scale_off + s.first_group * self.scale_es, s.n_groups * self.scale_es, s.scale_off))
+            out.append((self.file_off + s.a // 2, (s.b - s.a) // 2, s.packed_off))
+        return out
+
+    def landing_pieces(self) -> List[Tuple[int, int, int]]:
+        return self.nf4_pieces() if self.is_nf4 else self.int4_pieces()
+
+    def landing_span(self) -> Tuple[int, int]:
+        """``(offset, bytes)`` of the part of a 4-bit tensor's region that its landed inputs occupy."""
+        return (nf4 if self.is_nf4 else int4).landing_span(self.numel, self.group, self.scale_es)
 
     def int4_pieces(self) -> List[Tuple[int, int, int]]:
         """(file_off, bytes, region offset) of an INT4 tensor's landing pieces: per segment its
@@ -137,6 +174,9 @@ class LayerPlan:
                 runs.append(self._int4_run(path, pl, infos))
                 continue
             ti: TensorInfo = infos[key]
+            if key == pl.hf_name and nf4.is_nf4_source(key, infos):
+                runs.append(self._nf4_run(path, pl, infos))
+                continue
             if ti.dtype == torch.int8:
                 raise AssertionError("int8 not supported (need to add fp16_statistics)")   # utils.py:129
             if ti.dtype not in _SRC_ES:
@@ -157,6 +197,7 @@ class LayerPlan:
         self.file_bytes = sum(r.file_nbytes for r in self.runs)
         self.fp8_tensors = sum(1 for r in self.runs if r.is_fp8)
         self.int4_tensors = sum(1 for r in self.runs if r.is_int4)
+        self.nf4_tensors = sum(1 for r in self.runs if r.is_nf4)
         self.ignored_scales = sorted(k for k in infos if k.endswith(".input_scale"))
 
     @staticmethod
@@ -190,6 +231,26 @@ class LayerPlan:
         return TensorRun(pl.hf_name, ti.begin, pl.offset, pl.numel, ti.dtype, group=g, scale_off=si.begin,
                          scale_dtype=si.dtype)
 
+    @staticmethod
+    def _nf4_run(path: str, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
+        """The run of the bitsandbytes 4-bit tensor that feeds placement ``pl``.  The quant state and
+        the small tables (code books, nested absmax) are read now; the absmax bytes are read with the
+        weights, every pass."""
+        where = f"{path}: "
+
+        def read(name: str) -> torch.Tensor:
+            ti = infos[name]
+            raw = torch.empty(ti.nbytes, dtype=torch.uint8)
+            hostmem.pread_into(path, ti.begin, ti.nbytes, raw)
+            return raw.view(ti.dtype)
+
+        qs = nf4.check_entry(pl.hf_name, infos, pl.shape, read, where)
+        ti, ai = infos[pl.hf_name], infos[qs.absmax_name]
+        if ti.nbytes != pl.numel // 2 or ai.nbytes != pl.numel // qs.block * qs.absmax_es:
+            raise ValueError(f"{path}: {pl.hf_name} / {qs.absmax_name} byte sizes do not match their shapes")
+        return TensorRun(pl.hf_name, ti.begin, pl.offset, pl.numel, ti.dtype, group=qs.block, scale_off=ai.begin,
+                         scale_dtype=_ABSMAX_DTYPE[qs.absmax_kind], quant=qs)
+
     def pieces(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
         """(file_off, file_bytes, dst_off, kind) covering image bytes [lo, hi); dst_off relative to lo.
         lo / hi must be even (whole fp16 elements)."""
@@ -201,11 +262,12 @@ class LayerPlan:
             a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
             if a >= b:
                 continue
-            if r.is_int4:
+            if r.lands_segmented:
                 if (a, b) != (r.img_off, r.img_off + 2 * r.numel):
-                    raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the INT4 tensor "
-                                     f"{r.hf_name} (an INT4 tensor loads whole)")
-                out += [(fo, nb, r.img_off + do - lo, KIND_RAW) for fo, nb, do in r.int4_pieces()]
+                    fmt = "NF4" if r.is_nf4 else "INT4"
+                    raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the {fmt} tensor "
+                                     f"{r.hf_name} (an {fmt} tensor loads whole)")
+                out += [(fo, nb, r.img_off + do - lo, KIND_RAW) for fo, nb, do in r.landing_pieces()]
                 continue
             if r.is_fp8:
                 if (a, b) != (r.img_off, r.img_off + 2 * r.numel):
@@ -216,7 +278,7 @@ class LayerPlan:
             e0, e1 = (a - r.img_off) // 2, (b - r.img_off) // 2
             out.append((r.file_off + e0 * r.src_es, (e1 - e0) * r.src_es, a - lo,
                         KIND_F32 if r.src_dtype == torch.float32 else KIND_RAW))
-        if self.int4_tensors:
+        if self.int4_tensors or self.nf4_tensors:
             out.sort(key=lambda p: p[0])      # (the streamer reads pieces in file order)
         return out
 
@@ -246,6 +308,12 @@ class LayerPlan:
         hi = self.nbytes if hi is None else hi
         return [(r.img_off - lo, r) for r in self.runs
                 if r.is_int4 and r.img_off >= lo and r.img_off + 2 * r.numel <= hi]
+
+    def nf4_runs(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, TensorRun]]:
+        """(region offset relative to lo, run) of the NF4 tensors within [lo, hi)."""
+        hi = self.nbytes if hi is None else hi
+        return [(r.img_off - lo, r) for r in self.runs
+                if r.is_nf4 and r.img_off >= lo and r.img_off + 2 * r.numel <= hi]
 
 
 def _relabel_layer(infos: Dict[str, TensorInfo], layer_name: str) -> Dict[str, TensorInfo]:
@@ -297,6 +365,7 @@ class FileLayerSource(LayerSource):
         self._scale_arena: Optional[torch.Tensor] = None     # FP8 scales on the device (prepare_device)
         self._scales: Optional[Dict[Tuple[str, str], torch.Tensor]] = None
         self._scales_dev = None
+        self._nf4_tables: Dict[Tuple[str, str], Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]] = {}
         self.read_seconds = 0.0
         self.read_bytes = 0
 
@@ -338,6 +407,11 @@ class FileLayerSource(LayerSource):
         for off, r in pl.int4_runs(lo, hi):
             from ..ops import get_ops
             get_ops(torch.device("cpu")).dequant_int4(b[off:off + 2 * r.numel], r.numel, r.group, r.scale_dtype)
+        for off, r in pl.nf4_runs(lo, hi):
+            from ..ops import get_ops
+            q = r.quant
+            get_ops(torch.device("cpu")).dequant_nf4(b[off:off + 2 * r.numel], r.numel, q.block, q.absmax_kind, q.code,
+                                                     q.code2, q.nested_absmax, q.nested_block, q.offset)
         self.read_bytes += sum(p[1] for p in pieces)
         self.read_seconds += time.perf_counter() - t0
 
@@ -402,14 +476,23 @@ class FileLayerSource(LayerSource):
         """In-place bf16 -> fp16 of the bf16 tensors in image bytes [lo, hi) of ``dst``, whose byte 0
         is image byte ``lo`` (current stream)."""
         pl = self.plan(name)
-        runs, f8, i4 = pl.bf16_runs(lo, hi), pl.fp8_runs(lo, hi), pl.int4_runs(lo, hi)
-        if not runs and not f8 and not i4:
+        runs, f8, i4, n4 = pl.bf16_runs(lo, hi), pl.fp8_runs(lo, hi), pl.int4_runs(lo, hi), pl.nf4_runs(lo, hi)
+        if not runs and not f8 and not i4 and not n4:
             return
         from ..ops import get_ops
         ops = get_ops(dst.device)
         for off, r in i4:
             # INT4 tensors: expanded to fp16 in place in their own regions; the scales landed with them
             ops.dequant_int4(dst[off:off + 2 * r.numel], r.numel, r.group, r.scale_dtype)
+        if n4:
+            # NF4 tensors: expanded the same way; the absmax bytes landed with them, the small tables
+            # are resident in the table arena
+            self.prepare_device(dst.device)
+            for off, r in n4:
+                q = r.quant
+                code, code2, nested = self._nf4_tables[(name, r.hf_name)]
+                ops.dequant_nf4(dst[off:off + 2 * r.numel], r.numel, q.block, q.absmax_kind, code, code2, nested,
+                                q.nested_block, q.offset)
         for off, nb in runs:
             v = dst[off:off + nb]
             ops.cast_f16(v, v, 1)
@@ -422,9 +505,11 @@ class FileLayerSource(LayerSource):
     # ------------------------------------------------------------ FP8 scales
     def prepare_device(self, device) -> Dict[Tuple[str, str], torch.Tensor]:
         """The device-resident scale arena: the fp32 scales of every FP8 tensor of this source's
-        layers in ONE allocation, filled when the source first sees the device (the runner calls
-        this before it plans its VRAM, so a cap sees the arena in the measured context).  Returns
-        {(layer, tensor name): fp32 view}."""
+        layers, and the small tables of every NF4 tensor (code book, ``code2``, nested absmax;
+        identical code books stored once), in ONE allocation, filled when the source first sees the
+        device (the runner calls this before it plans its VRAM, so a cap sees the arena in the
+        measured context).  Returns {(layer, tensor name): fp32 view} of the FP8 scales; the NF4
+        tables are ``_nf4_tables[(layer, tensor name)] = (code, code2, nested_absmax)``."""
         device = torch.device(device)
         with self._lock:
             if self._scales is not None and self._scales_dev == device:
@@ -432,16 +517,33 @@ class FileLayerSource(LayerSource):
         if self._scales is not None and self._scales_dev != device:
             raise RuntimeError("one streaming source serves one device")
         parts, index, off = [], {}, 0
+        nf4_index, books = {}, {}
+
+        def add(t: torch.Tensor) -> Tuple[int, int]:
+            nonlocal off
+            cnt, at = t.numel(), off
+            parts.append(t)
+            pad = -cnt % 4                         # every vector 16-byte aligned
+            if pad:
+                parts.append(torch.zeros(pad, dtype=torch.float32))
+            off += cnt + pad
+            return at, cnt
+
+        def book(t: torch.Tensor) -> Tuple[int, int]:
+            key = t.numpy().tobytes()              # (16 or 256 floats: identical code books once)
+            if key not in books:
+                books[key] = add(t)
+            return books[key]
+
         for n in self.names:
             for r in self.plan(n).runs:
                 if r.is_fp8:
-                    cnt = r.scale.numel()
-                    index[(n, r.hf_name)] = (off, cnt)
-                    parts.append(r.scale)
-                    pad = -cnt % 4                 # every scale vector 16-byte aligned
-                    if pad:
-                        parts.append(torch.zeros(pad, dtype=torch.float32))
-                    off += cnt + pad
+                    index[(n, r.hf_name)] = add(r.scale)
+                elif r.is_nf4:
+                    q = r.quant
+                    u8 = q.absmax_kind == nf4.ABSMAX_U8
+                    nf4_index[(n, r.hf_name)] = (book(q.code), book(q.code2) if u8 else None,
+                                                 add(q.nested_absmax) if u8 else None)
         views: Dict[Tuple[str, str], torch.Tensor] = {}
         arena = None
         if parts:
@@ -453,8 +555,10 @@ class FileLayerSource(LayerSource):
             else:
                 arena = host
             views = {k: arena[o:o + c] for k, (o, c) in index.items()}
+        tables = {k: tuple(None if oc is None else arena[oc[0]:oc[0] + oc[1]] for oc in v) for k, v in nf4_index.items()}
         with self._lock:
             self._scale_arena, self._scales, self._scales_dev = arena, views, device
+            self._nf4_tables = tables
         return views
 
     def scale_arena_bytes(self) -> int:
@@ -467,6 +571,10 @@ class FileLayerSource(LayerSource):
     def int4_tensors(self) -> int:
         """INT4 tensors among this source's layers."""
         return sum(self.plan(n).int4_tensors for n in self.names)
+
+    def nf4_tensors(self) -> int:
+        """bitsandbytes 4-bit tensors among this source's layers."""
+        return sum(self.plan(n).nf4_tensors for n in self.names)
 
     def file_bytes(self, names: Optional[Sequence[str]] = None) -> int:
         """Tensor bytes of the layer files (what a pass reads and copies)."""
@@ -492,6 +600,7 @@ class FileLayerSource(LayerSource):
             _native.runtime().fls_streamer_destroy(self._streamer)
             self._streamer = None
         self._scale_arena = self._scales = self._scales_dev = None
+        self._nf4_tables = {}
 
     def __del__(self):
         try:

@@ -17,8 +17,9 @@ Here a source yields the *packed* layer image (see :mod:`..models.layout`):
   weights (generated on the GPU and copied down) for the 70B benchmark.
 * :class:`CompactHostStore` — an FP8 or INT4 checkpoint's file bytes resident in
   pinned host memory, FP8 as FP8 (half the RAM and PCIe bytes), INT4 as nibbles
-  and raw scales (a quarter), copied tensor by tensor to their landing positions
-  and expanded to fp16 in the HBM slot (:mod:`..fp8`, :mod:`..int4`).
+  and raw scales (a quarter), NF4 as packed bytes and raw absmax bytes, copied
+  tensor by tensor to their landing positions and expanded to fp16 in the HBM
+  slot (:mod:`..fp8`, :mod:`..int4`, :mod:`..nf4`).
 * data-parallel scatter-load (:func:`piece_slices`): a rank keeps only its
   1/G byte-slice of every layer piece; the layer (or one piece of it) is
   re-assembled in HBM with an RCCL all-gather over xGMI
@@ -32,7 +33,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, int4
+from .. import _native
 from ..config import ModelConfig
 from ..models.layout import LayerLayout, layer_kind, layer_layout
 from . import hostmem
@@ -244,7 +245,8 @@ class CompactHostStore(LayerSource):
 
     An INT4 tensor (:mod:`..int4`) is pinned as its landing image: the nibbles and raw scales of its
     segments, each at a 16-byte aligned offset, in the order they take in the tensor's region, so the
-    whole tensor is still one H2D (``int4.landing_span``)."""
+    whole tensor is still one H2D (``int4.landing_span``); a bitsandbytes 4-bit tensor
+    (:mod:`..nf4`) likewise, with its raw absmax bytes for scales."""
 
     norms_folded = False
     COMPACT_ALIGN = 16
@@ -262,9 +264,9 @@ class CompactHostStore(LayerSource):
             offs, off, pieces = {}, 0, []
             for r in pl.runs:
                 offs[r.hf_name] = off
-                if r.is_int4:
-                    base, span = int4.landing_span(r.numel, r.group, r.scale_es)
-                    pieces += [(fo, nb, off + do - base, st.KIND_RAW) for fo, nb, do in r.int4_pieces()]
+                if r.lands_segmented:
+                    base, span = r.landing_span()
+                    pieces += [(fo, nb, off + do - base, st.KIND_RAW) for fo, nb, do in r.landing_pieces()]
                     off += self._aligned(span)
                     continue
                 f32 = r.src_dtype == torch.float32
@@ -302,7 +304,7 @@ class CompactHostStore(LayerSource):
         return self.files.plan(name)
 
     def fold_norms(self, device):
-        raise ValueError("--weight_cache host keeps an FP8 or INT4 checkpoint's bytes as they are in the files: norms "
+        raise ValueError("--weight_cache host keeps an FP8, INT4 or NF4 checkpoint's bytes as they are in the files: norms "
                          "cannot be folded into quantised weights (they are folded as each layer lands)")
 
     def read_into(self, name: str, dst: torch.Tensor) -> None:
@@ -318,15 +320,15 @@ class CompactHostStore(LayerSource):
         expansions.  Returns the host bytes copied."""
         pl = self.files.plan(name)
         hi = pl.nbytes if hi is None else hi
-        pl.pieces(lo, hi)                   # (refuses a range through an FP8 or INT4 tensor)
+        pl.pieces(lo, hi)                   # (refuses a range through a quantised tensor)
         buf, offs, total = self.buffers[name], self._offsets[name], 0
         with torch.cuda.stream(stream):
             for r in pl.runs:
                 a, b = max(lo, r.img_off), min(hi, r.img_off + 2 * r.numel)
                 if a >= b:
                     continue
-                if r.is_int4:
-                    base, span = int4.landing_span(r.numel, r.group, r.scale_es)
+                if r.lands_segmented:
+                    base, span = r.landing_span()
                     src, d0 = buf[offs[r.hf_name]:offs[r.hf_name] + span], r.img_off + base - lo
                 elif r.is_fp8:
                     src, d0 = buf[offs[r.hf_name]:offs[r.hf_name] + r.numel], r.land_off - lo

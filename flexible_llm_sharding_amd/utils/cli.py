@@ -166,7 +166,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lora", type=str, default=None, metavar="DIR",
                    help="a LoRA adapter in PEFT's saved form (adapter_config.json + adapter_model.safetensors), merged "
                         "into the weights in HBM as they land (W += s B A, lora.py); the base checkpoint is read as it "
-                        "is, fp16 / bf16, FP8 or INT4")
+                        "is, fp16 / bf16, FP8, INT4 or NF4 (bitsandbytes 4-bit: the QLoRA base)")
     p.add_argument("--lora_scale", type=float, default=None,
                    help="multiplies the adapter's scale alpha / r (default 1.0; needs --lora)")
     p.add_argument("--max_token_len", type=int, default=None,

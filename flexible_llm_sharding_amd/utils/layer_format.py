@@ -99,7 +99,8 @@ def _load_shard(path: str) -> Dict[str, torch.Tensor]:
 
 
 def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize: str = None,
-                      fp8_scale: str = "channel", int4_group: int = 128, int4_scale_dtype=torch.float16) -> List[str]:
+                      fp8_scale: str = "channel", int4_group: int = 128, int4_scale_dtype=torch.float16,
+                      nf4_block: int = 64, nf4_double_quant: bool = True) -> List[str]:
     """Convert an HF checkpoint directory into per-layer safetensors files.
 
     An FP8 (e4m3fn) source checkpoint passes through unchanged: its scale tensors (``weight_scale``,
@@ -108,9 +109,12 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
     scales (fp8.quantize_state_dict).  An INT4 (W4A16) source checkpoint passes through too, its
     ``weight_packed`` / ``weight_scale`` / ``weight_shape`` tensors in their weight's layer file;
     ``quantize="int4"`` writes the same weights as INT4 in groups of ``int4_group`` with
-    ``int4_scale_dtype`` scales (int4.quantize_state_dict)."""
-    if quantize not in (None, "fp8", "int4"):
-        raise ValueError(f"--quantize {quantize!r}: fp8 or int4")
+    ``int4_scale_dtype`` scales (int4.quantize_state_dict).  A bitsandbytes 4-bit source checkpoint
+    passes through with its bytes unchanged, the companions of a weight (``X.weight.absmax``,
+    ``.quant_map``, ``.nested_*``, ``.quant_state.bitsandbytes__nf4``) in its layer file;
+    ``quantize="nf4"`` writes that form from float weights (nf4.quantize_state_dict)."""
+    if quantize not in (None, "fp8", "int4", "nf4"):
+        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4")
     os.makedirs(out_dir, exist_ok=True)
     for fn in glob.glob(os.path.join(src_dir, "*")):
         base = os.path.basename(fn)
@@ -157,7 +161,10 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
             sd[canonical_param(p)] = cache[wmap[p]][p]
         assert len(sd) == len(layer_params[l]), f"Should have {len(layer_params[l])} keys for {l}"
         out_sd = normalize_expert_names(model_type, sd)
-        if quantize == "int4":
+        if quantize == "nf4":
+            from ..nf4 import quantize_state_dict as quantize_nf4
+            out_sd = quantize_nf4(out_sd, nf4_block, nf4_double_quant)
+        elif quantize == "int4":
             from ..int4 import quantize_state_dict as quantize_int4
             out_sd = quantize_int4(out_sd, int4_group, int4_scale_dtype)
         elif quantize:

@@ -111,10 +111,13 @@ def split_projections(cfg: ModelConfig, sd: Dict[str, torch.Tensor]) -> Dict[str
 def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
                                std: float = 0.02, dtype=torch.float16, unique_layers: int = 0,
                                device="cpu", progress=None, quantize: str = None, fp8_scale: str = "channel",
-                               int4_group: int = 128, int4_scale_dtype=torch.float16) -> None:
+                               int4_group: int = 128, int4_scale_dtype=torch.float16, nf4_block: int = 64,
+                               nf4_double_quant: bool = True) -> None:
     """``quantize="fp8"``: the decoder layers' projection weights are written as FP8 (e4m3fn) with
     ``fp8_scale`` (channel | tensor | block128) scales (fp8.quantize_state_dict); ``quantize="int4"``:
-    as INT4 words in groups of ``int4_group`` with ``int4_scale_dtype`` scales (int4.quantize_state_dict).
+    as INT4 words in groups of ``int4_group`` with ``int4_scale_dtype`` scales (int4.quantize_state_dict);
+    ``quantize="nf4"``: in the bitsandbytes 4-bit form, NF4 code book, blocks of ``nf4_block``, the
+    absmax 8-bit quantised if ``nf4_double_quant`` (nf4.quantize_state_dict).
     ``unique_layers`` > 0: only the first K decoder layers get their own random weights;
     decoder layer i >= K is a hard link to layer i % K (a 138 GB 70B checkpoint in ~K x 1.7 GB of
     disk for streaming benchmarks — the reads are per file, as for a real checkpoint)."""
@@ -136,17 +139,21 @@ def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
                 continue
         sd = synthetic_layer_state_dict(cfg, name, seed, std, dtype, device)
         if quantize:
-            sd = _quantized(sd, quantize, fp8_scale, int4_group, int4_scale_dtype)
+            sd = _quantized(sd, quantize, fp8_scale, int4_group, int4_scale_dtype, nf4_block, nf4_double_quant)
         save_file(sd, path)
 
 
 def _quantized(sd: Dict[str, torch.Tensor], quantize: str, fp8_scale: str, int4_group: int = 128,
-               int4_scale_dtype=torch.float16) -> Dict[str, torch.Tensor]:
+               int4_scale_dtype=torch.float16, nf4_block: int = 64,
+               nf4_double_quant: bool = True) -> Dict[str, torch.Tensor]:
+    if quantize == "nf4":
+        from ..nf4 import quantize_state_dict as quantize_nf4
+        return quantize_nf4(sd, nf4_block, nf4_double_quant)
     if quantize == "int4":
         from ..int4 import quantize_state_dict as quantize_int4
         return quantize_int4(sd, int4_group, int4_scale_dtype)
     if quantize != "fp8":
-        raise ValueError(f"--quantize {quantize!r}: fp8 or int4")
+        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4")
     from ..fp8 import quantize_state_dict
     return quantize_state_dict(sd, fp8_scale)
 

@@ -8,6 +8,8 @@
                  (decoder projection weights as FP8 e4m3 + fp32 scales: half the weight bytes)
                  --quantize int4 [--int4_group 128] [--int4_scale_dtype float16|bfloat16|float32]
                  (the same weights as 4-bit words + group scales, W4A16: a quarter of the bytes)
+                 --quantize nf4 [--nf4_block 64] [--nf4_double_quant true|false]
+                 (the same weights in the bitsandbytes 4-bit form, NF4 code book: the QLoRA base)
     python prepare_weights.py <model_dir> <new_file_dir> --merge_lora <adapter_dir> [--lora_scale 1.0]
                  (the fp16 checkpoint with a LoRA adapter merged in: what --lora computes in HBM)
 """
@@ -31,10 +33,10 @@ def main(argv=None):
                     help="--synthetic: checkpoint dtype")
     ap.add_argument("--unique_layers", type=int, default=0,
                     help="--synthetic: write K distinct decoder layers, hard-link the rest (disk-limited boxes)")
-    ap.add_argument("--quantize", choices=["fp8", "int4"], default=None,
+    ap.add_argument("--quantize", choices=["fp8", "int4", "nf4"], default=None,
                     help="write the decoder layers' 2-D projection weights (q/k/v/o, gate/up/down, fused and "
-                         "expert weights) as FP8 e4m3 with fp32 scales, or as INT4 (W4A16, symmetric) with group "
-                         "scales; router, norms, biases, embedding and head stay as they are")
+                         "expert weights) as FP8 e4m3 with fp32 scales, as INT4 (W4A16, symmetric) with group "
+                         "scales, or as bitsandbytes 4-bit (NF4 code book, block absmax); router, norms, biases, embedding and head stay as they are")
     ap.add_argument("--fp8_scale", choices=["channel", "tensor", "block128"], default="channel",
                     help="--quantize fp8: one scale per output channel / per tensor (weight_scale) or per "
                          "128x128 block (weight_scale_inv)")
@@ -43,6 +45,10 @@ def main(argv=None):
                          "(0: one scale per output channel)")
     ap.add_argument("--int4_scale_dtype", choices=["float16", "bfloat16", "float32"], default="float16",
                     help="--quantize int4: dtype of the group scales")
+    ap.add_argument("--nf4_block", type=int, default=64,
+                    help="--quantize nf4: weights per absmax block, a multiple of 32 that divides every tensor's size")
+    ap.add_argument("--nf4_double_quant", choices=["true", "false"], default="true",
+                    help="--quantize nf4: store the absmax values 8-bit quantised in nested blocks of 256")
     ap.add_argument("--merge_lora", type=str, default=None, metavar="DIR",
                     help="write bin_dir (per-layer files or an HF directory of safetensors files, fp16 / bf16 / "
                          "fp32) with the LoRA adapter DIR merged into its weights, as fp16: the twin of a run with "
@@ -74,11 +80,13 @@ def main(argv=None):
         write_synthetic_checkpoint(preset(a.bin_dir, **kw), a.new_file_dir, seed=a.seed, std=a.std,
                                    dtype=getattr(torch, a.dtype), unique_layers=a.unique_layers,
                                    quantize=a.quantize, fp8_scale=a.fp8_scale, int4_group=a.int4_group,
-                                   int4_scale_dtype=getattr(torch, a.int4_scale_dtype))
+                                   int4_scale_dtype=getattr(torch, a.int4_scale_dtype), nf4_block=a.nf4_block,
+                                   nf4_double_quant=a.nf4_double_quant == "true")
     else:
         import torch
         split_into_layers(a.bin_dir, a.new_file_dir, quantize=a.quantize, fp8_scale=a.fp8_scale,
-                          int4_group=a.int4_group, int4_scale_dtype=getattr(torch, a.int4_scale_dtype))
+                          int4_group=a.int4_group, int4_scale_dtype=getattr(torch, a.int4_scale_dtype),
+                          nf4_block=a.nf4_block, nf4_double_quant=a.nf4_double_quant == "true")
     return 0
 
 

@@ -1,0 +1,664 @@
+"""bitsandbytes 4-bit (NF4 / FP4) checkpoints without a GPU: the value rule against literal known
+answers and an independent numpy oracle (tests/nf4_ref.py), the landing layout and an emulation of
+the in-place launch chain, the native host code's mirror of the layout, the loader and ``main.py``
+against the fp16 twin, the converter, and every refusal."""
+import ctypes
+import json
+import os
+import pickle
+import shutil
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import nf4_ref as nr  # noqa: E402
+
+from flexible_llm_sharding_amd import nf4  # noqa: E402
+from flexible_llm_sharding_amd.config import preset  # noqa: E402
+from flexible_llm_sharding_amd.models.layout import pack_layer  # noqa: E402
+from flexible_llm_sharding_amd.runtime.stream import FileLayerSource, LayerPlan  # noqa: E402
+from flexible_llm_sharding_amd.runtime.weights import CompactHostStore  # noqa: E402
+from flexible_llm_sharding_amd.utils.layer_format import layer_file, split_into_layers  # noqa: E402
+from flexible_llm_sharding_amd.utils.safetensors_io import load_file, save_file  # noqa: E402
+from flexible_llm_sharding_amd.utils.synthetic import write_synthetic_checkpoint  # noqa: E402
+from flexible_llm_sharding_amd.utils.tokenizer import load_tokenizer  # noqa: E402
+
+T = nf4.TAIL
+CODE = torch.tensor(nr.NF4, dtype=torch.float32)
+
+
+def _bits(w: torch.Tensor):
+    return [int(x) & 0xFFFF for x in w.reshape(-1).view(torch.int16).tolist()]
+
+
+def _deq(by, absmax, block, n=None, **kw):
+    """nf4.dequantize of literal bytes, padded with zero bytes to one block."""
+    by = list(by)
+    n = n or block
+    packed = torch.tensor(by + [0] * (n // 2 - len(by)), dtype=torch.uint8)
+    return nf4.dequantize(packed, CODE, absmax, (1, n), block, **kw)
+
+
+# ------------------------------------------------------------------ literal known answers
+def test_published_code_book():
+    assert tuple(nf4.NF4_CODE) == nr.NF4 and len(nr.NF4) == 16
+    assert all(float(np.float32(x)) == x for x in nr.NF4)               # (fp32 values, typed exactly)
+
+
+def test_known_answers_f32_absmax():
+    two = torch.tensor([2.0], dtype=torch.float32)
+    assert _bits(_deq([0x0F], two, 32))[:2] == [0xC000, 0x4000]           # (-2.0, 2.0): high nibble first
+    assert _bits(_deq([0xF0], two, 32))[:2] == [0x4000, 0xC000]           # (2.0, -2.0)
+    assert _bits(_deq([0x7F], two, 32))[:2] == [0x0000, 0x4000]           # (+0, 2.0)
+    assert _bits(_deq([0x7F], torch.tensor([-2.0]), 32))[:2] == [0x8000, 0xC000]     # 0 * negative is -0
+    assert _bits(_deq([0x0F], torch.tensor([1e5]), 32))[:2] == [0xFC00, 0x7C00]      # overflow to -inf, +inf
+    # a second block takes the second absmax
+    w = _deq([0xFF] * 16 + [0xFF] * 16, torch.tensor([2.0, 3.0]), 32, n=64)
+    assert _bits(w)[31:33] == [0x4000, 0x4200]
+
+
+def test_known_answers_u8_absmax():
+    code2 = torch.zeros(256, dtype=torch.float32)
+    code2[200] = 0.5
+    kw = dict(code2=code2, nested_absmax=torch.tensor([4.0]), nested_block=256, offset=0.25)
+    w = _deq([0xFF], torch.tensor([200], dtype=torch.uint8), 32, **kw)    # s = 0.5 * 4 + 0.25 = 2.25
+    assert _bits(w)[0] == 0x4080
+    # with B2 = 2 the third block takes the second nested absmax: s = 0.5 * 4, 0.5 * 4, 0.5 * 16 (+ 0.25)
+    kw = dict(code2=code2, nested_absmax=torch.tensor([4.0, 16.0]), nested_block=2, offset=0.25)
+    w = _deq([0xFF] * 48, torch.tensor([200, 200, 200], dtype=torch.uint8), 32, n=96, **kw)
+    assert _bits(w)[31::32] == [0x4080, 0x4080, 0x4820]                   # 2.25, 2.25, 8.25
+
+
+def test_multiply_then_add_is_not_a_fused_multiply_add():
+    """a = b = (1 + 2^-23) 2^20: a b = 2^40 (1 + 2^-22 + 2^-46) rounds to 2^40 + 2^18 in fp32, and with
+    offset -(2^40 + 2^18) the separately rounded sum is +0 while fmaf(a, b, offset) is 2^-6 (0x2400)."""
+    a = float(np.float32(1 + 2.0 ** -23) * np.float32(2.0 ** 20))
+    off = -(2.0 ** 40 + 2.0 ** 18)
+    assert float(np.float32(off)) == off
+    exact = a * a + off                                                   # (fp64 holds the product exactly)
+    assert exact == 2.0 ** -6
+    code2 = np.zeros(256, dtype=np.float32)
+    code2[7] = a
+    q, nested = np.array([7], dtype=np.uint8), np.array([a], dtype=np.float32)
+    want = nr.ref_dequant(nr.pack(np.full(32, 15)), nr.NF4, q, 32, 32, code2, nested, 1, off)
+    assert _bits(want)[0] == 0x0000
+    got = _deq([0xFF], torch.from_numpy(q), 32, code2=torch.from_numpy(code2), nested_absmax=torch.from_numpy(nested),
+               nested_block=1, offset=off)
+    assert _bits(got)[0] == 0x0000 != 0x2400
+
+
+# ------------------------------------------------------------------ every nibble, every position
+@pytest.mark.parametrize("kind", ["f32", "u8"])
+@pytest.mark.parametrize("block", [64, 128, 4096])
+def test_every_nibble_in_every_position(block, kind):
+    rng = np.random.default_rng(block + (kind == "u8"))
+    n = max(2 * block, 1024)                          # (16 values x 32 positions need 512 weights)
+    nib = nr.lanes(n)
+    assert {(int(u), i % 32) for i, u in enumerate(nib)} == {(u, p) for u in range(16) for p in range(32)}
+    packed = nr.pack(nib)
+    for code in (np.array(nr.NF4, dtype=np.float32), nr.full_mantissa_code(rng)):
+        for extreme in (False, True):
+            if kind == "f32":
+                absmax, kw, tkw = nr.f32_absmax(n // block, rng, extreme), {}, {}
+            else:
+                absmax, code2, nested, off = nr.u8_absmax(n // block, 3, rng, extreme)
+                kw = dict(code2=code2, nested=nested, b2=3, offset=off)
+                tkw = dict(code2=nr.t(code2), nested_absmax=nr.t(nested), nested_block=3, offset=off)
+            want = nr.ref_dequant(packed, code, absmax, n, block, **kw)
+            got = nf4.dequantize(nr.t(packed), nr.t(code), nr.t(absmax), (n // 32, 32), block, **tkw)
+            assert nr.same_bits(got, want), (block, kind, extreme)
+
+
+def test_special_results_are_reached():
+    """-0, fp16 subnormals, overflow to +-inf and an exact rounding tie all occur in the extreme pool
+    (so the comparisons above and on the GPU do cover them)."""
+    n, block = 32 * len(nr.EXTREME), 32
+    absmax = np.array(nr.EXTREME, dtype=np.float32)
+    w = nr.ref_dequant(nr.pack(nr.lanes(n)), nr.NF4, absmax, n, block)
+    bits = np.array(_bits(w))
+    assert (bits == 0x8000).any() and (bits == 0x7C00).any() and (bits == 0xFC00).any()
+    assert ((bits & 0x7C00) == 0)[(bits & 0x3FF) != 0].any()             # a subnormal
+    tie = nr.ref_dequant(nr.pack(np.full(32, 15)), nr.NF4, np.array([1 + 2.0 ** -11], dtype=np.float32), 32, 32)
+    above = nr.ref_dequant(nr.pack(np.full(32, 15)), nr.NF4, np.array([1 + 2.0 ** -11 + 2.0 ** -23], dtype=np.float32), 32, 32)
+    assert _bits(tie)[0] == 0x3C00 and _bits(above)[0] == 0x3C01          # the tie goes to even
+
+
+# ------------------------------------------------------------------ landing layout
+NS = (64, 128, 8128, 8192, 8256, 24896, 16448, 49216, 8192 * 28672)
+LAYOUT_CASES = [(n, b, es) for n in NS for b in (64, 128, 256, 4096) if n % b == 0 for es in (1, 4)]
+
+
+@pytest.mark.parametrize("n,block,es", LAYOUT_CASES)
+def test_landing_layout(n, block, es):
+    lay = nf4.region_layout(n, block, es)
+    sched = nf4.schedule(n, block, es)
+    assert sched == [(s.a, s.b) for s in lay]
+    assert sched[0][0] == 0 and sched[-1][1] == n and all(x[1] == y[0] for x, y in zip(sched, sched[1:]))
+    assert all(a % 32 == 0 and b % 32 == 0 and a < b for a, b in sched) and sched[-1][1] - sched[-1][0] <= T
+    spans = []
+    for j, s in enumerate(lay):
+        assert s.packed_off % 16 == 0 and s.scale_off % 16 == 0 and s.scale_off >= 0
+        assert (s.first_group, s.n_groups) == (s.a // block, s.b // block - s.a // block)
+        if j + 1 < len(lay):
+            assert 2 * s.b <= s.scale_off                                 # writes stay below everything unread
+        spans += [(s.scale_off, s.scale_off + s.n_groups * es), (s.packed_off, s.packed_off + (s.b - s.a) // 2)]
+    assert all(x[1] <= y[0] for x, y in zip(spans, spans[1:])) and spans[-1][1] == 2 * n     # no overlap, in order
+    blocks = [k for s in lay for k in range(s.first_group, s.first_group + s.n_groups)] if n < 10 ** 6 else None
+    if blocks is not None:
+        assert blocks == list(range(n // block))                          # every absmax in exactly one segment
+    assert sum(s.n_groups for s in lay) == n // block
+    assert nf4.landing_span(n, block, es) == (lay[0].scale_off, 2 * n - lay[0].scale_off)
+    if n == 8192 * 28672 and block == 64:
+        assert len(lay) == (9 if es == 1 else 10)
+
+
+def test_layout_argument_checks():
+    for bad in ((64, 48, 1), (96, 64, 1), (64, 32, 2), (64, 0, 4), (64, 32, 3)):
+        with pytest.raises(ValueError):
+            nf4.region_layout(*bad)
+    assert nf4.region_layout(0, 64, 1) == ()
+    from flexible_llm_sharding_amd import int4
+    for es in (1, 3):                                                     # INT4 keeps refusing other scale sizes
+        with pytest.raises(ValueError):
+            int4.region_layout(64, 32, es)
+    assert int4.region_layout(8256, 64, 4) == nf4.region_layout(8256, 64, 4)
+
+
+def test_native_host_code_mirrors_the_layout():
+    """fls_dequant_nf4_segment equals nf4.region_layout segment for segment (host code, launches nothing)."""
+    from flexible_llm_sharding_amd import _native
+    k = _native.kernels()
+    assert k.fls_dequant_nf4_tail() == T
+    out = (ctypes.c_uint64 * 6)()
+    for n, block, es in LAYOUT_CASES + [(8192 * 8192, 64, 1), (8192 * 8192, 64, 4)]:
+        lay = nf4.region_layout(n, block, es)
+        assert k.fls_dequant_nf4_launches(n, block, es) == len(lay)
+        for j, s in enumerate(lay):
+            assert k.fls_dequant_nf4_segment(n, block, es, j, ctypes.addressof(out)) == 0
+            assert tuple(out) == tuple(s), (n, block, es, j)
+        assert k.fls_dequant_nf4_segment(n, block, es, len(lay), ctypes.addressof(out)) != 0
+    assert k.fls_dequant_nf4_launches(96, 64, 1) < 0 and k.fls_dequant_nf4_launches(64, 48, 1) < 0
+    assert k.fls_dequant_nf4_launches(64, 32, 2) < 0 and k.fls_dequant_nf4_launches(0, 64, 1) == 0
+    assert k.fls_dequant_int4_launches(64, 32, 1) < 0                     # (INT4's own check is unchanged)
+
+
+def _emulate(region: np.ndarray, n: int, block: int, es: int, code, code2, nested, b2, off) -> np.ndarray:
+    """Run the chain launch by launch on the byte buffer: read ALL of a launch's sources (its packed
+    bytes from its own segment; each absmax entry from the segment that holds its block), then write
+    ALL of its outputs.  A write over a byte some later launch still needs shows as a wrong result."""
+    lay = nf4.region_layout(n, block, es)
+    where = np.zeros(n // block, dtype=np.int64)
+    for s in lay:
+        where[s.first_group:s.first_group + s.n_groups] = s.scale_off + np.arange(s.n_groups) * es
+    c = np.asarray(code, dtype=np.float32)
+    for s in lay:
+        by = region[s.packed_off:s.packed_off + (s.b - s.a) // 2].copy()
+        ks = np.arange(s.a // block, (s.b - 1) // block + 1)
+        raw = region[where[ks][:, None] + np.arange(es)].reshape(-1).copy()
+        with np.errstate(over="ignore", invalid="ignore"):
+            if es == 4:
+                sc = raw.view(np.float32)
+            else:
+                sc = (code2[raw] * nested[ks // b2]).astype(np.float32) + np.float32(off)
+            i = np.arange(s.a, s.b)
+            u = np.where(i % 2 == 0, by[(i - s.a) // 2] >> 4, by[(i - s.a) // 2] & 15)
+            w = (c[u] * sc[i // block - ks[0]]).astype(np.float32).astype(np.float16)
+        region[2 * s.a:2 * s.b] = np.frombuffer(w.tobytes(), dtype=np.uint8)
+    return region
+
+
+@pytest.mark.parametrize("n,block,es", [c for c in LAYOUT_CASES if c[0] < 10 ** 6])
+def test_in_place_emulation(n, block, es):
+    rng = np.random.default_rng(n + block + es)
+    packed = rng.integers(0, 256, n // 2).astype(np.uint8)
+    code = nr.full_mantissa_code(rng)
+    if es == 4:
+        absmax, code2, nested, b2, off = nr.f32_absmax(n // block, rng, False), None, None, 0, 0.0
+    else:
+        b2 = 5
+        absmax, code2, nested, off = nr.u8_absmax(n // block, b2, rng, False)
+    want = nr.ref_dequant(packed, code, absmax, n, block, code2, nested, b2, off)
+    region = torch.full((2 * n,), 0x5A, dtype=torch.uint8)                # stale bytes of the last occupant
+    nf4.land(region, nr.t(packed), nr.t(absmax).view(torch.uint8), n, block, es)
+    assert (region[:nf4.landing_span(n, block, es)[0]] == 0x5A).all()
+    got = _emulate(region.numpy().copy(), n, block, es, code, code2, nested, b2, off)
+    assert nr.same_bits(torch.from_numpy(got).view(torch.float16), want)
+    # the torch backend expands the same landed bytes
+    from flexible_llm_sharding_amd.ops import get_ops
+    get_ops(torch.device("cpu")).dequant_nf4(region, n, block, nf4.ABSMAX_F32 if es == 4 else nf4.ABSMAX_U8, nr.t(code),
+                                             None if es == 4 else nr.t(code2), None if es == 4 else nr.t(nested), b2, off)
+    assert nr.same_bits(region.view(torch.float16), want)
+
+
+# ------------------------------------------------------------------ loader
+@pytest.fixture(scope="module")
+def pairs(tmp_path_factory):
+    root = tmp_path_factory.mktemp("nf4_pairs")
+    return lambda name, dq: nr.make_pair(root, name, dq)
+
+
+@pytest.mark.parametrize("dq", [True, False])
+def test_loader_gives_the_twins_image(pairs, dq):
+    cfg, q, twin = pairs("tiny", dq)
+    es = 1 if dq else 4
+    lname = "model.layers.1"
+    plan = LayerPlan(cfg, lname, layer_file(q, lname))
+    sd = load_file(layer_file(q, lname))
+    assert plan.nf4_tensors == 7 == sum(".quant_state." in k for k in sd) and plan.int4_tensors == plan.fp8_tensors == 0
+    assert plan.file_bytes == nr.moved_bytes(q, lname)
+    for r in plan.runs:
+        if r.is_nf4:
+            assert not r.is_int4 and r.group == 64 and r.scale_es == es
+            assert r.file_nbytes == r.numel // 2 + r.numel // 64 * es
+            base, span = nf4.landing_span(r.numel, 64, es)
+            ps = r.nf4_pieces()
+            assert sum(p[1] for p in ps) == r.file_nbytes and min(p[2] for p in ps) == base
+    pieces = plan.pieces()
+    assert sum(p[1] for p in pieces) == plan.file_bytes and all(p[3] == 0 for p in pieces)      # KIND_RAW
+    assert [p[0] for p in pieces] == sorted(p[0] for p in pieces)        # file order, as the streamer reads
+    r = next(r for r in plan.runs if r.is_nf4)
+    for lo, hi in ((r.img_off + 2, r.img_off + 2 * r.numel), (0, r.img_off + r.numel)):
+        with pytest.raises(ValueError, match="NF4"):
+            plan.pieces(lo, hi)
+    src = FileLayerSource(cfg, q)
+    store = CompactHostStore(FileLayerSource(cfg, q), pinned=False)
+    for n in cfg.layer_names():
+        want = pack_layer(cfg, n, load_file(layer_file(twin, n)))
+        for s in (src, store):
+            got = torch.zeros(src.nbytes(n), dtype=torch.uint8)
+            s.read_into(n, got)
+            assert torch.equal(got, want), n
+        assert torch.equal(pack_layer(cfg, n, load_file(layer_file(q, n))), want), n
+    assert src.nf4_tensors() == 14 and src.file_bytes() == sum(nr.moved_bytes(q, n) for n in cfg.layer_names())
+    # the compact store pins each NF4 tensor as its landing image
+    a16 = lambda x: (x + 15) // 16 * 16                                   # noqa: E731
+    want = sum(sum(a16(p[1]) for p in r.nf4_pieces()) if r.is_nf4 else a16(r.numel * min(r.src_es, 2))
+               for n in cfg.layer_names() for r in store.plan(n).runs)
+    assert store.total_bytes == want
+    r = next(r for r in store.plan(lname).runs if r.is_nf4)
+    base, span = r.landing_span()
+    off = store._offsets[lname][r.hf_name]
+    region = torch.zeros(2 * r.numel, dtype=torch.uint8)
+    region[base:] = store.buffers[lname][off:off + span]
+    packed, raw = nf4.unland(region, r.numel, 64, es)
+    assert torch.equal(packed, sd[r.hf_name].reshape(-1)) and torch.equal(raw, sd[r.hf_name + ".absmax"].view(torch.uint8))
+    # the table arena: code books once, nested absmax per tensor
+    src.prepare_device("cpu")
+    n_nested = sum(-(-r.quant.nested_absmax.numel() // 4) * 4 for n in cfg.layer_names() for r in src.plan(n).runs
+                   if r.is_nf4 and dq)
+    assert src.scale_arena_bytes() == 4 * (16 + (256 + n_nested if dq else 0))
+
+
+def _scores(cfg, src, path, prompts, **kw):
+    from flexible_llm_sharding_amd.engine import ShardedRunner
+    r = ShardedRunner(cfg, src, "cpu", load_tokenizer(path), **kw)
+    out = r(prompts)
+    r.close()
+    return out
+
+
+@pytest.mark.parametrize("name,dq", [("tiny", True), ("tiny", False), ("tiny-qwen2", True)])
+def test_engine_nf4_bitwise_equals_twin_cpu(pairs, name, dq):
+    cfg, q, twin = pairs(name, dq)
+    prompts = nr.prompts_for(cfg)
+    want = _scores(cfg, FileLayerSource(cfg, twin), twin, prompts)
+    for lnps in (1, 3):
+        got = _scores(cfg, FileLayerSource(cfg, q), q, prompts, layer_num_per_shard=lnps)
+        compact = _scores(cfg, CompactHostStore(FileLayerSource(cfg, q), pinned=False), q, prompts,
+                          layer_num_per_shard=lnps)
+        for w, a, b in zip(want, got, compact):
+            assert w.dtype == np.float16
+            assert np.array_equal(w.view(np.uint16), a.view(np.uint16))
+            assert np.array_equal(w.view(np.uint16), b.view(np.uint16))
+    if name == "tiny" and dq:                  # (the quantisation is not a no-op)
+        orig = os.path.join(os.path.dirname(q), "orig")
+        write_synthetic_checkpoint(cfg, orig, seed=3, std=0.05)
+        o = _scores(cfg, FileLayerSource(cfg, orig), orig, prompts)
+        assert any(not np.array_equal(x, y) for x, y in zip(o, want))
+
+
+# ------------------------------------------------------------------ main.py, converter
+def _env():
+    return dict(os.environ, PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+
+
+def _main(args, cwd):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "main.py")] + args, cwd=cwd, env=_env(),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r
+
+
+@pytest.fixture(scope="module")
+def cli_pair(tmp_path_factory):
+    """prepare_weights.py --synthetic tiny --quantize nf4 (double quantisation), its twin and prompts."""
+    d = tmp_path_factory.mktemp("nf4_cli")
+    q, twin = str(d / "q"), str(d / "twin")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "prepare_weights.py"), "tiny", q, "--synthetic",
+                        "--quantize", "nf4", "--std", "0.05"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    nf4.write_twin(q, twin)
+    cfg = preset("tiny")
+    pp = d / "prompts.pkl"
+    pickle.dump(nr.prompts_for(cfg, 4), open(pp, "wb"))
+    return cfg, q, twin, pp, d
+
+
+@pytest.mark.parametrize("tag,extra", [("score", []), ("gen3", ["--num_gen_token", "3"])])
+def test_main_nf4_equals_twin(cli_pair, tag, extra):
+    cfg, q, twin, pp, d = cli_pair
+    want = d / f"twin_{tag}.pkl"
+    _main(["--model_path", twin, "--prompt_pickle", str(pp), "--output_file", str(want)] + extra, str(d))
+    for mode in ("host", "stream"):
+        out, mj = d / f"{mode}_{tag}.pkl", d / f"{mode}_{tag}.json"
+        _main(["--model_path", q, "--prompt_pickle", str(pp), "--output_file", str(out), "--metrics_json", str(mj),
+               "--weight_cache", mode] + extra, str(d))
+        assert open(out, "rb").read() == open(want, "rb").read(), (tag, mode)
+        m = json.load(open(mj))
+        assert m["nf4_tensors"] == 14 and m["int4_tensors"] == 0 and m["fp8_tensors"] == 0
+        assert m["weight_file_bytes"] == sum(nr.moved_bytes(q, n) for n in cfg.layer_names())
+        if mode == "host":                      # pinned as the files' bytes, not as the fp16 image
+            assert m["weight_file_bytes"] <= m["weight_pinned_bytes"] < m["weight_file_bytes"] + 16 * 200
+
+
+def test_main_lora_on_nf4_equals_lora_on_twin(cli_pair):
+    from flexible_llm_sharding_amd import lora
+    cfg, q, twin, pp, d = cli_pair
+    ad = str(d / "adapter")
+    lora.write_synthetic_adapter(cfg, ad, r=4, seed=1)
+    outs = {}
+    for tag, path in (("nf4", q), ("twin", twin), ("plain", q)):
+        out = d / f"lora_{tag}.pkl"
+        _main(["--model_path", path, "--prompt_pickle", str(pp), "--output_file", str(out)]
+              + ([] if tag == "plain" else ["--lora", ad]), str(d))
+        outs[tag] = open(out, "rb").read()
+    assert outs["nf4"] == outs["twin"] != outs["plain"]
+    # --merge_lora refuses the 4-bit source with the message of the other quantised bases
+    with pytest.raises(TypeError, match="_proj.weight.*merge a quantised checkpoint's fp16 twin"):
+        lora.write_twin(q, lora.LoraAdapter.load(cfg, ad), str(d / "merged"))
+
+
+W = "model.layers.0.mlp.down_proj.weight"
+COMPANIONS = (".absmax", ".quant_map", ".nested_absmax", ".nested_quant_map", ".quant_state.bitsandbytes__nf4")
+
+
+def test_converter_writes_the_five_companion_form(cli_pair, tmp_path):
+    cfg, q, twin, pp, d = cli_pair
+    sd = load_file(layer_file(q, "model.layers.0"))
+    n = 256 * 512
+    assert sd[W].dtype == torch.uint8 and tuple(sd[W].shape) == (n // 2, 1)
+    assert all(W + c in sd for c in COMPANIONS)
+    assert sd[W + ".quant_map"].tolist() == [float(np.float32(x)) for x in nr.NF4]
+    assert sd[W + ".absmax"].dtype == torch.uint8 and tuple(sd[W + ".absmax"].shape) == (n // 64,)
+    assert sd[W + ".nested_absmax"].dtype == torch.float32 and tuple(sd[W + ".nested_absmax"].shape) == (n // 64 // 256,)
+    c2 = sd[W + ".nested_quant_map"]
+    assert c2.dtype == torch.float32 and tuple(c2.shape) == (256,) and bool((c2[1:] > c2[:-1]).all())
+    assert {-1.0, 0.0, 1.0} <= set(c2.tolist())
+    js = json.loads(bytes(sd[W + ".quant_state.bitsandbytes__nf4"].tolist()).decode())
+    assert js["quant_type"] == "nf4" and js["blocksize"] == 64 and js["shape"] == [256, 512]
+    assert js["nested_blocksize"] == 256 and isinstance(js["nested_offset"], float) and "dtype" in js
+    assert "model.layers.0.input_layernorm.weight" in sd
+    assert all(v.dtype == torch.float16 for v in load_file(layer_file(q, "model.embed_tokens")).values())
+    tw = load_file(layer_file(twin, "model.layers.0"))
+    assert not any(nf4.is_companion_name(k) for k in tw) and tw[W].dtype == torch.float16
+    assert nf4.weight_of_companion(W + COMPANIONS[4]) == W == nf4.weight_of_companion(W + ".nested_absmax")
+    # --nf4_double_quant false: three companions, fp32 absmax
+    f = nf4.quantize(torch.randn(64, 64), 128, False)
+    assert set(f) == {"", ".absmax", ".quant_map", ".quant_state.bitsandbytes__nf4"} and f[".absmax"].dtype == torch.float32
+    # a checkpoint already in the form converts with unchanged bytes, quantization_config included
+    hf, out = str(tmp_path / "hf"), str(tmp_path / "layers")
+    os.makedirs(hf)
+    full = {}
+    for name in cfg.layer_names():
+        full.update(load_file(layer_file(q, name)))
+    save_file(full, os.path.join(hf, "model.safetensors"))
+    for fn in os.listdir(q):
+        if not fn.endswith(".safetensors"):
+            shutil.copy(os.path.join(q, fn), os.path.join(hf, fn))
+    conf = json.load(open(os.path.join(hf, "config.json")))
+    conf["quantization_config"] = {"quant_method": "bitsandbytes", "load_in_4bit": True, "bnb_4bit_quant_type": "nf4"}
+    json.dump(conf, open(os.path.join(hf, "config.json"), "w"))
+    for kw in ({}, {"quantize": "nf4"}):                                  # (--quantize nf4 leaves a 4-bit directory as it is)
+        shutil.rmtree(out, ignore_errors=True)
+        split_into_layers(hf, out, verbose=False, **kw)
+        for name in cfg.layer_names():
+            a, b = load_file(layer_file(q, name)), load_file(layer_file(out, name))
+            assert sorted(a) == sorted(b) and all(a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]) for k in a), name
+    assert json.load(open(os.path.join(out, "config.json")))["quantization_config"]["load_in_4bit"] is True
+    from flexible_llm_sharding_amd.config import ModelConfig
+    assert FileLayerSource(ModelConfig.from_pretrained(out), out).nf4_tensors() == 14
+
+
+@pytest.mark.parametrize("dq", [False, True])
+def test_converter_error_bound(dq):
+    """|w - w16| <= absmax (h + 2^-23) + |c| e + r, each term from the tables the writer used:
+
+    * h is the largest half-gap of the code book (0.1519 for NF4, between its two lowest entries):
+      the writer takes the entry nearest to x = fp32(w / absmax), which lies in [-1, 1], the span of
+      the code book, so |x - c| <= h; the fp32 division and the fp32 product c s each add at most a
+      relative 2^-24 of a value no larger than absmax, hence 2^-23.
+    * e bounds |s - absmax|, 0 for an fp32 absmax.  With double quantisation the writer rounds
+      (absmax - offset) / nested to the nearest entry of its code2, whose largest half-gap is h2
+      (1/254), so |absmax - offset - code2[q] nested| <= nested h2; the subtraction, the division,
+      the product code2[q] nested and the sum with the offset are four fp32 roundings of values no
+      larger than nested (three) or than |s| (one): e = nested (h2 + 3 x 2^-24) + 2^-24 (absmax + e),
+      taken as nested (h2 + 2^-22) + 2^-23 absmax.  |c| <= 1.
+    * r is the fp16 rounding of a value of magnitude at most absmax + e: half a unit in the last
+      place, 2^-11 of it, and 2^-25 (half the subnormal spacing) at least."""
+    gen = torch.Generator().manual_seed(7)
+    w = (torch.randn(256, 512, generator=gen) * 0.05).to(torch.float16)
+    w[3, :64] = 0                                                         # an all-zero block: absmax 1
+    w[5, 7] = 30.0                                                        # an outlier block
+    sd = {"model.layers.0.mlp.down_proj.weight": w}
+    q = nf4.quantize_state_dict(sd, 64, dq)
+    assert (W + ".nested_absmax" in q) == dq
+    w16 = nf4.dequantize_entry(q, W, (256, 512)).to(torch.float64)
+    absmax = w.to(torch.float64).reshape(-1, 64).abs().amax(-1)
+    absmax = torch.where(absmax == 0, torch.ones_like(absmax), absmax)
+    code = q[W + ".quant_map"].to(torch.float64)
+    h = float(((code[1:] - code[:-1]) / 2).max())
+    assert abs(h - (1.0 - 0.6961928009986877) / 2) < 1e-12
+    e = torch.zeros_like(absmax)
+    if dq:
+        c2 = q[W + ".nested_quant_map"].to(torch.float64)
+        h2 = float(((c2[1:] - c2[:-1]) / 2).max())
+        assert abs(h2 - 1 / 254) < 2.0 ** -24                          # (fp32 entries: each within 2^-25 of k / 127)
+        nested = q[W + ".nested_absmax"].to(torch.float64).repeat_interleave(256)[:absmax.numel()]
+        e = nested * (h2 + 2.0 ** -22) + 2.0 ** -23 * absmax
+    r = torch.clamp(2.0 ** -11 * (absmax + e), min=2.0 ** -25)
+    bound = (absmax * (h + 2.0 ** -23) + e + r).reshape(-1, 1)
+    err = (w.to(torch.float64) - w16).abs().reshape(-1, 64)
+    print("largest err / bound:", float((err / bound).max()))
+    assert bool((err <= bound).all())
+    assert float(w16[3, :64].abs().max()) <= float(bound.reshape(-1)[3 * 8])      # (the zero block stays within its bound)
+    # ties go to the lower index: a code book of eighths, absmax 1, weights on exact midpoints
+    eighths = [k / 8 for k in range(-8, 8)]
+    t = torch.zeros(1, 64)
+    t[0, 0], t[0, 1], t[0, 2], t[0, 3] = -1.0, 0.0625, 0.0626, -0.0625
+    by = nf4.quantize(t, 64, False, code=eighths)[""].reshape(-1)
+    assert [int(by[0]) >> 4, int(by[0]) & 15, int(by[1]) >> 4, int(by[1]) & 15] == [0, 8, 9, 7]
+
+
+# ------------------------------------------------------------------ refusals
+Q = "model.layers.0.self_attn.q_proj.weight"
+STATE = Q + ".quant_state.bitsandbytes__nf4"
+
+
+def _set_state(sd, **fields):
+    js = json.loads(bytes(sd[STATE].tolist()).decode())
+    for k, v in fields.items():
+        if v is None:
+            js.pop(k, None)
+        else:
+            js[k] = v
+    sd[STATE] = torch.tensor(list(json.dumps(js).encode()), dtype=torch.uint8)
+
+
+def _layer_with(tmp_path, cfg, edit, dq=True):
+    d = str(tmp_path / "m")
+    write_synthetic_checkpoint(cfg, d, seed=1, std=0.05, quantize="nf4", nf4_double_quant=dq)
+    p = layer_file(d, "model.layers.0")
+    sd = load_file(p)
+    edit(sd)
+    save_file(sd, p)
+    return d, p
+
+
+REFUSALS = ["bad_json", "not_an_object", "no_blocksize", "no_quant_type", "no_shape_field", "quant_type_int8", "wrong_shape",
+            "packed_shape", "packed_2d", "blocksize_48", "blocksize_not_dividing", "no_quant_map", "quant_map_f16",
+            "quant_map_17", "absmax_f16", "absmax_len", "no_absmax", "u8_no_nested_absmax", "u8_no_nested_quant_map",
+            "nested_quant_map_255", "nested_absmax_len", "no_nested_blocksize", "no_nested_offset", "nan_code",
+            "inf_nested", "inf_code2", "inf_offset"]
+
+
+@pytest.mark.parametrize("case", REFUSALS)
+def test_refused_nf4_tensors(tmp_path, case):
+    cfg = preset("tiny")
+
+    def edit(sd):
+        n = sd[Q].numel() * 2
+        if case == "bad_json":
+            sd[STATE] = torch.tensor(list(b'{"quant_type": "nf4", '), dtype=torch.uint8)
+        elif case == "not_an_object":
+            sd[STATE] = torch.tensor(list(b'[1, 2]'), dtype=torch.uint8)
+        elif case == "no_blocksize":
+            _set_state(sd, blocksize=None)
+        elif case == "no_quant_type":
+            _set_state(sd, quant_type=None)
+        elif case == "no_shape_field":
+            _set_state(sd, shape=None)
+        elif case == "quant_type_int8":
+            _set_state(sd, quant_type="int8")
+        elif case == "wrong_shape":
+            _set_state(sd, shape=[128, 512])
+        elif case == "packed_shape":
+            sd[Q] = sd[Q][:-1].contiguous()
+        elif case == "packed_2d":
+            sd[Q] = sd[Q].reshape(256, -1).contiguous()
+        elif case == "blocksize_48":
+            _set_state(sd, blocksize=48)
+        elif case == "blocksize_not_dividing":
+            _set_state(sd, blocksize=32 * 7)
+        elif case == "no_quant_map":
+            del sd[Q + ".quant_map"]
+        elif case == "quant_map_f16":
+            sd[Q + ".quant_map"] = sd[Q + ".quant_map"].to(torch.float16)
+        elif case == "quant_map_17":
+            sd[Q + ".quant_map"] = torch.zeros(17)
+        elif case == "absmax_f16":
+            sd[Q + ".absmax"] = torch.ones(n // 64, dtype=torch.float16)
+        elif case == "absmax_len":
+            sd[Q + ".absmax"] = sd[Q + ".absmax"][:-1].contiguous()
+        elif case == "no_absmax":
+            del sd[Q + ".absmax"]
+        elif case == "u8_no_nested_absmax":
+            del sd[Q + ".nested_absmax"]
+        elif case == "u8_no_nested_quant_map":
+            del sd[Q + ".nested_quant_map"]
+        elif case == "nested_quant_map_255":
+            sd[Q + ".nested_quant_map"] = sd[Q + ".nested_quant_map"][:255].contiguous()
+        elif case == "nested_absmax_len":
+            sd[Q + ".nested_absmax"] = torch.ones(sd[Q + ".nested_absmax"].numel() + 1)
+        elif case == "no_nested_blocksize":
+            _set_state(sd, nested_blocksize=None)
+        elif case == "no_nested_offset":
+            _set_state(sd, nested_offset=None)
+        elif case == "nan_code":
+            sd[Q + ".quant_map"][3] = float("nan")
+        elif case == "inf_nested":
+            sd[Q + ".nested_absmax"][0] = float("inf")
+        elif case == "inf_code2":
+            sd[Q + ".nested_quant_map"][9] = float("-inf")
+        else:
+            _set_state(sd, nested_offset=1e39)                            # (not finite in fp32)
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(TypeError, match="q_proj.weight"):
+        LayerPlan(cfg, "model.layers.0", p)
+    with pytest.raises(TypeError, match="q_proj.weight"):
+        pack_layer(cfg, "model.layers.0", load_file(p))
+
+
+def test_refused_u8_weight_without_quant_state(tmp_path):
+    """Refused as before this format was read: by dtype, naming the tensor."""
+    cfg = preset("tiny")
+    d, p = _layer_with(tmp_path, cfg, lambda sd: sd.pop(STATE))
+    with pytest.raises(TypeError, match="q_proj.weight has dtype torch.uint8"):
+        LayerPlan(cfg, "model.layers.0", p)
+
+
+def test_refused_eight_bit_bitsandbytes(tmp_path):
+    """LLM.int8() weights (I8 with SCB) stay refused the way int8 always was."""
+    cfg = preset("tiny")
+
+    def edit(sd):
+        for k in [k for k in sd if k.startswith(Q + ".")]:
+            del sd[k]
+        sd[Q] = torch.zeros(256, 256, dtype=torch.int8)
+        sd[Q[:-len("weight")] + "SCB"] = torch.ones(256)
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(AssertionError, match="int8 not supported"):
+        LayerPlan(cfg, "model.layers.0", p)
+    with pytest.raises(AssertionError, match="int8 not supported"):
+        pack_layer(cfg, "model.layers.0", load_file(p))
+
+
+def test_refused_non_2d_placement(tmp_path):
+    """A norm weight (1-D placement) stored 4-bit is refused by name."""
+    cfg = preset("tiny")
+    N = "model.layers.0.input_layernorm.weight"
+
+    def edit(sd):
+        for suf, t in nf4.quantize(torch.ones(1, 256), 64, False).items():
+            sd[N + suf] = t
+    d, p = _layer_with(tmp_path, cfg, edit)
+    with pytest.raises(TypeError, match="input_layernorm.weight"):
+        LayerPlan(cfg, "model.layers.0", p)
+    with pytest.raises(TypeError, match="input_layernorm.weight"):
+        pack_layer(cfg, "model.layers.0", load_file(p))
+
+
+def test_unlisted_family_accepts_the_companions(pairs):
+    import dataclasses
+    cfg, q, twin = pairs("tiny", True)
+    other = dataclasses.replace(cfg, model_type="some_llama_like")
+    assert LayerPlan(other, "model.layers.0", layer_file(q, "model.layers.0")).nf4_tensors == 7
+    sd = load_file(layer_file(q, "model.layers.0"))
+    sd["model.layers.0.self_attn.q_norm.weight.absmax"] = torch.zeros(4)          # (no such weight)
+    with pytest.raises(NotImplementedError):
+        pack_layer(other, "model.layers.0", sd)
+
+
+def test_refused_dp_weight_shard_and_host_sizing(pairs):
+    from flexible_llm_sharding_amd.api import build_runner, build_source, check_fp8_dp_shard, resolve_weight_cache
+    from flexible_llm_sharding_amd.models.layout import layer_kind, layer_layout
+    from flexible_llm_sharding_amd.parallel.comm import Comm
+    from flexible_llm_sharding_amd.utils.cli import parse_args
+    cfg, q, twin = pairs("tiny", True)
+    with pytest.raises(ValueError, match="--dp_weight_shard.*NF4"):
+        check_fp8_dp_shard(types.SimpleNamespace(model_path=q, synthetic=None, score_mode="next_token"), cfg)
+    check_fp8_dp_shard(types.SimpleNamespace(model_path=twin, synthetic=None, score_mode="next_token"), cfg)
+    args = parse_args(["--model_path", q, "--prompt_pickle", "p.pkl", "--output_file", "o.pkl", "--data_parallel",
+                       "--dp_weight_shard", "true"])
+    with pytest.raises(ValueError, match="--dp_weight_shard"):
+        build_runner(args, cfg, "cpu", types.SimpleNamespace(world=2, rank=0, active=True), load_tokenizer(q))
+    # --weight_cache host is sized by file bytes
+    names, comm = cfg.layer_names(), Comm(0, 1)
+    src, tsrc = FileLayerSource(cfg, q), FileLayerSource(cfg, twin)
+    image = sum(layer_layout(cfg, layer_kind(n)).nbytes for n in names)
+    assert src.file_bytes() < image / 2
+    between = (src.file_bytes() + image) / 2 / 1e9
+
+    def a(mode, path=q):
+        return types.SimpleNamespace(weight_cache=mode, host_mem_gb=between, synthetic=None, model_path=path,
+                                     layer_num_per_shard=1, data_parallel=False, verbose=False)
+    assert resolve_weight_cache(a("auto"), cfg, comm, names, sliced=False, source=src) == "host"
+    assert resolve_weight_cache(a("auto"), cfg, comm, names, sliced=False, source=tsrc) == "stream"
+    st = build_source(a("host"), cfg, comm, torch.device("cpu"))
+    assert isinstance(st, CompactHostStore) and st.files.nf4_tensors() == 14 and st.norms_folded is False
+    assert isinstance(build_source(a("stream"), cfg, comm, torch.device("cpu")), FileLayerSource)
