@@ -36,6 +36,7 @@
 #include <string>
 #include <thread>
 #include <unistd.h>
+#include <utility>
 #include <vector>
 
 extern "C" int fls_rt_version(void) { return 1; }
@@ -557,6 +558,7 @@ struct Streamer {
   double read_s = 0, wait_s = 0;
   uint64_t read_bytes = 0, h2d_bytes = 0;
   int direct_fallbacks = 0;
+  int fail_direct_read = 0;   // host streamers (tests): the next O_DIRECT chunk read fails with this
 };
 
 struct SubPiece {
@@ -646,6 +648,15 @@ extern "C" int fls_streamer_sync_host(void* h) {
   return 0;
 }
 
+// host streamer: the next chunk read with O_DIRECT fails with `err` (< 0) instead of reading, as
+// the kernel fails it where it cannot pin the ring's pages (-EFAULT)
+extern "C" int fls_streamer_fail_direct_read(void* h, int err) {
+  auto* st = (Streamer*)h;
+  if (!st || !st->host || err >= 0) return -1;
+  st->fail_direct_read = err;
+  return 0;
+}
+
 extern "C" uint64_t fls_streamer_pinned_bytes(void* h) {
   auto* st = (Streamer*)h;
   return st ? (uint64_t)st->slots.size() * (st->chunk + 2 * kAlign) : 0;
@@ -709,12 +720,17 @@ extern "C" int64_t fls_streamer_load(void* h, const char* path, const fls_piece_
       rlo = lo / kAlign * kAlign;
       rhi = (hi + kAlign - 1) / kAlign * kAlign;
     }
-    int64_t r = pool_read(st->pool, fd, rlo, rhi, sl.buf, hi);
-    if (r == -EINVAL && direct) {
-      // the file system refused O_DIRECT for this range: buffered from here on
+    int64_t r = direct && st->fail_direct_read ? std::exchange(st->fail_direct_read, 0)
+                                               : pool_read(st->pool, fd, rlo, rhi, sl.buf, hi);
+    if ((r == -EINVAL || r == -EFAULT) && direct) {
+      // O_DIRECT refused: by the file system for this range (EINVAL), or because the kernel
+      // cannot pin the ring's pages for the transfer (EFAULT: pinned host memory that is a
+      // device mapping, as in a virtual machine with the GPU passed through) -- then for every
+      // file, so the streamer stops asking.  Buffered from here on.
       close(fd);
       fd = open(path, flags);
       if (fd < 0) return -errno;
+      if (r == -EFAULT) st->direct = 0;
       direct = false;
       ++st->direct_fallbacks;
       rlo = lo;

@@ -5,7 +5,11 @@
 // (persistent pread pool + pinned chunk ring + asynchronous copies, on its
 // GPU-free host copy engine: ring wrap-around and slot reuse, O_DIRECT and its
 // buffered fallback, fp32 -> fp16 pieces, pieces split across chunks) without a GPU.
+#include <fcntl.h>
+#include <unistd.h>
+
 #include <cassert>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -155,6 +159,41 @@ int main(int argc, char** argv) {
         CHECK(fls_streamer_stats(sh, &rs, &ws, &rb, &hb, &fb_n) == 0);
         CHECK(rb > 0 && hb > 0 && fb_n >= 0);
         fls_streamer_destroy(sh);
+      }
+    }
+    // an O_DIRECT read the kernel fails because it cannot pin the ring's pages (EFAULT): that chunk
+    // is read again buffered, the load is complete, and the streamer asks for O_DIRECT no more
+    {
+      void* sd = fls_streamer_create_host(1u << 20, 2, 4, 1, 0);
+      CHECK(sd != nullptr);
+      const int probe = open(lf.c_str(), O_RDONLY | O_DIRECT);     // (tmpfs refuses O_DIRECT at open)
+      if (probe >= 0) close(probe);
+      if (sd) {
+        CHECK(fls_streamer_fail_direct_read(sd, -EFAULT) == 0);
+        double rs, ws;
+        uint64_t rb, hb;
+        for (int rep = 0; rep < 2; ++rep) {
+          std::vector<uint8_t> got(dst, 0);            // (as `want` between the pieces)
+          CHECK(fls_streamer_load(sd, lf.c_str(), pcs.data(), (int)pcs.size(), got.data(), nullptr) > 0);
+          CHECK(fls_streamer_sync_host(sd) == 0);
+          CHECK(std::memcmp(got.data(), want.data(), dst) == 0);
+          int fb_n = -1;
+          CHECK(fls_streamer_stats(sd, &rs, &ws, &rb, &hb, &fb_n) == 0);
+          if (probe >= 0) CHECK(fb_n == 1);          // one fallback, none on the second load
+        }
+        // any other read error still fails the load
+        void* se = fls_streamer_create_host(1u << 20, 2, 4, 1, 0);
+        CHECK(se != nullptr);
+        if (se) {
+          std::vector<uint8_t> got(dst, 0);
+          CHECK(fls_streamer_fail_direct_read(se, -EIO) == 0);
+          const int64_t r = fls_streamer_load(se, lf.c_str(), pcs.data(), (int)pcs.size(), got.data(), nullptr);
+          CHECK(probe >= 0 ? r == -EIO : r > 0);
+          CHECK(fls_streamer_sync_host(se) == 0);
+          fls_streamer_destroy(se);
+        }
+        CHECK(fls_streamer_fail_direct_read(sd, 5) != 0);
+        fls_streamer_destroy(sd);
       }
     }
     // a larger chunk with several pread granules per chunk (8 MiB granules, 20 MiB chunk)

@@ -3,7 +3,7 @@
 * :func:`alloc_host` — exact-size pinned buffers from ``hipHostMalloc``
   (PyTorch's caching host allocator rounds to powers of two: a 1.71 GB 70B
   layer would take 2 GB), wrapped as uint8 CPU tensors; falls back to
-  pageable memory when no GPU is present.
+  pageable memory when no GPU is present, or when the runtime refuses to pin more.
 * :func:`read_safetensors` — header via the native index, tensor bytes with
   the multi-threaded ``pread`` engine into one host buffer, zero-copy views.
 """
@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes
 import os
 import time
+import warnings
 from typing import Dict
 
 import torch
@@ -29,6 +30,11 @@ pinned_peak = 0
 # buffers, not allocate; engine stats report the per-call counts)
 alloc_calls = 0
 alloc_seconds = 0.0
+# pinned requests the runtime refused (the machine pins less memory than it has: a virtual
+# machine's GPU aperture, a locked-memory limit) and the bytes handed out pageable instead
+pinned_refusals = 0
+pageable_bytes = 0
+_live_blocks = set()         # start addresses of the live hipHostMalloc blocks
 
 
 def _count(n: int) -> None:
@@ -42,16 +48,23 @@ class _PinnedOwner:
 
     def __init__(self, ptr, lib, n):
         self.ptr, self.lib, self.n = ptr, lib, n
+        _live_blocks.add(ptr)
         _count(n)
 
     def __del__(self):
         try:
             if self.ptr:
                 self.lib.fls_pinned_free(self.ptr)
+                _live_blocks.discard(self.ptr)
                 self.ptr = None
                 _count(-self.n)
         except Exception:
             pass
+
+
+def is_pinned_block(t: torch.Tensor) -> bool:
+    """``t`` starts a live pinned block of :func:`alloc_host` (not a pageable stand-in)."""
+    return t.data_ptr() in _live_blocks
 
 
 def _gpu_present() -> bool:
@@ -67,22 +80,33 @@ def alloc_host(nbytes: int, pinned: bool = True) -> torch.Tensor:
     The pinned block is owned by a ctypes array object that every tensor view
     keeps alive (``torch.frombuffer`` holds a reference), so the memory is
     ``hipHostFree``d exactly when the last view dies.
+
+    Where the runtime refuses to pin another ``nbytes`` (a machine may pin far less than its
+    RAM) the buffer is pageable: copies to and from the device stay correct, they are staged by
+    the HIP runtime and block the host.  ``pinned_refusals`` / ``pageable_bytes`` count these,
+    and the first one warns.
     """
     if pinned and _gpu_present():
-        global alloc_calls, alloc_seconds
+        global alloc_calls, alloc_seconds, pinned_refusals, pageable_bytes
         rt = _native.runtime_or_none()
-        if rt is not None:
-            n = max(1, nbytes)
-            t0 = time.perf_counter()
-            ptr = rt.fls_pinned_alloc(n)
-            alloc_calls += 1
-            alloc_seconds += time.perf_counter() - t0
-            if ptr:
-                arr_t = type("PinnedBlock", (ctypes.c_uint8 * n,), {})
-                arr = arr_t.from_address(ptr)
-                arr.owner = _PinnedOwner(ptr, rt, n)
-                return torch.frombuffer(arr, dtype=torch.uint8)[:nbytes]
-        return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        if rt is None:
+            return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        n = max(1, nbytes)
+        t0 = time.perf_counter()
+        ptr = rt.fls_pinned_alloc(n)
+        alloc_calls += 1
+        alloc_seconds += time.perf_counter() - t0
+        if ptr:
+            arr_t = type("PinnedBlock", (ctypes.c_uint8 * n,), {})
+            arr = arr_t.from_address(ptr)
+            arr.owner = _PinnedOwner(ptr, rt, n)
+            return torch.frombuffer(arr, dtype=torch.uint8)[:nbytes]
+        if not pinned_refusals:
+            warnings.warn(f"hipHostMalloc refused {n / 1e9:.2f} GB with {pinned_live / 1e9:.2f} GB pinned: "
+                          "this buffer, and any other it refuses, is pageable (slower copies)",
+                          RuntimeWarning, stacklevel=2)
+        pinned_refusals += 1
+        pageable_bytes += nbytes
     return torch.empty(nbytes, dtype=torch.uint8)
 
 

@@ -331,7 +331,8 @@ class FileLayerSource(LayerSource):
 
     ``chunk_mb`` x ``n_chunks`` is the whole pinned host footprint of the weight path.
     ``direct`` reads with ``O_DIRECT`` (bypassing the page cache; falls back to buffered
-    reads where the file system refuses it).
+    reads where the file system refuses it, or where the kernel cannot pin the ring's pages for
+    a direct transfer; ``stats()["direct_fallbacks"]`` counts them).
     """
 
     def __init__(self, cfg: ModelConfig, model_path: str, names: Optional[Sequence[str]] = None,

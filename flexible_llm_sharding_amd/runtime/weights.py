@@ -69,6 +69,7 @@ class HostStore(LayerSource):
     # lora_at_build: the store holds whole fp16 layers, so an adapter is merged once (merge_lora)
     lora_merged = None
     lora_at_build = True
+    _pinning_full = False       # hipHostMalloc refused a layer: the rest of the store is pageable
 
     def __init__(self, cfg: ModelConfig, dtype=torch.float16, pinned: bool = True,
                  names: Optional[Sequence[str]] = None):
@@ -144,9 +145,29 @@ class HostStore(LayerSource):
         src = self.buffers[name]
         dst[:src.numel()].copy_(src)
 
+    # pinned memory handed back when the store meets the machine's pinning limit: the engine pins
+    # more after the store is built (activation pools, staging buffers, score read-back)
+    PINNED_HEADROOM = 4 << 30
+
     def alloc(self, name: str) -> torch.Tensor:
-        buf = hostmem.alloc_host(self.nbytes(name), pinned=self.pinned)
+        refused = hostmem.pinned_refusals
+        buf = hostmem.alloc_host(self.nbytes(name), pinned=self.pinned and not self._pinning_full)
         self.buffers[name] = buf
+        if hostmem.pinned_refusals != refused:
+            # the machine pins no more: this layer is pageable, and the store asks for no pinned
+            # memory again (the H2D copies of pageable layers are staged by the runtime).  The
+            # last pinned layers move to pageable memory too, so what the engine pins later
+            # finds PINNED_HEADROOM bytes free
+            self._pinning_full = True
+            freed = 0
+            for n in reversed(list(self.buffers)):
+                if freed >= self.PINNED_HEADROOM:
+                    break
+                old = self.buffers[n]
+                if hostmem.is_pinned_block(old):
+                    self.buffers[n] = torch.empty_like(old).copy_(old)
+                    freed += old.numel()
+                    del old
         return buf
 
     @classmethod

@@ -74,6 +74,67 @@ def test_pwrite_pread_roundtrip(tmp_path):
     assert torch.equal(z, x[12345:12445])
 
 
+class _LimitedPinner:
+    """A runtime that pins at most ``limit`` bytes (malloc'd), as a machine with a small pinning
+    limit does; everything else is the real runtime."""
+
+    def __init__(self, limit):
+        import ctypes
+        self.libc = ctypes.CDLL("libc.so.6")
+        self.libc.malloc.restype, self.libc.malloc.argtypes = ctypes.c_void_p, [ctypes.c_size_t]
+        self.libc.free.argtypes = [ctypes.c_void_p]
+        self.limit, self.live = limit, {}
+
+    def fls_pinned_alloc(self, n):
+        if sum(self.live.values()) + n > self.limit:
+            return None
+        p = self.libc.malloc(n)
+        self.live[p] = n
+        return p
+
+    def fls_pinned_free(self, p):
+        del self.live[p]
+        self.libc.free(p)
+        return 0
+
+
+def test_host_store_outlives_the_pinning_limit(monkeypatch):
+    """The machine pins less than the store needs (8 equal decoder layers, room for 4.5 of them):
+    the layer that is refused and every later one are pageable, the last pinned layers are handed
+    back (PINNED_HEADROOM: two layers here), nothing a buffer held is lost, and afterwards a
+    buffer of the headroom's size can still be pinned."""
+    from flexible_llm_sharding_amd.config import preset
+    from flexible_llm_sharding_amd.runtime.weights import HostStore
+    cfg = preset("tiny", num_hidden_layers=8)
+    st = HostStore(cfg, pinned=True)
+    nb = [st.nbytes(n) for n in st.names]          # embed, 8 decoder layers, norm, head
+    dec = nb[1]
+    assert nb[1:9] == [dec] * 8 and nb[9] + nb[10] < dec
+    rt = _LimitedPinner(nb[0] + 4 * dec + dec // 2)
+    monkeypatch.setattr(hostmem, "_gpu_present", lambda: True)
+    monkeypatch.setattr(_native, "runtime_or_none", lambda: rt)
+    monkeypatch.setattr(hostmem, "pinned_refusals", 0)
+    monkeypatch.setattr(hostmem, "pageable_bytes", 0)
+    monkeypatch.setattr(HostStore, "PINNED_HEADROOM", 2 * dec)
+    live0 = hostmem.pinned_live
+    with pytest.warns(RuntimeWarning, match="hipHostMalloc refused"):
+        for i, n in enumerate(st.names):
+            st.alloc(n).fill_(i + 1)
+    pinned = [hostmem.is_pinned_block(st.buffers[n]) for n in st.names]
+    # decoder layer 4 was refused; layers 3 and 2 made room; nothing after the refusal is pinned,
+    # not even the norm and the head, which would fit
+    assert pinned == [True, True, True] + [False] * 8
+    assert hostmem.pinned_refusals == 1 and hostmem.pageable_bytes == dec
+    assert hostmem.pinned_live - live0 == nb[0] + 2 * dec == sum(rt.live.values())
+    for i, n in enumerate(st.names):
+        assert st.buffers[n].numel() == nb[i] and bool((st.buffers[n] == i + 1).all())
+    later = hostmem.alloc_host(2 * dec)            # what the engine pins after the store is built
+    assert hostmem.is_pinned_block(later) and hostmem.pinned_refusals == 1
+    del later
+    st.buffers.clear()
+    assert not rt.live and hostmem.pinned_live == live0
+
+
 def test_gather_blocks():
     rt = _native.runtime()
     src = torch.arange(64, dtype=torch.int32)
