@@ -253,6 +253,20 @@ int fls_dequant_nf4_launches(uint64_t n, uint64_t block, int absmax_es);
 int fls_dequant_nf4_tail(void);
 // launch j of that chain: out[6] = {a, b, packed offset, absmax offset, first block, blocks} (host only)
 int fls_dequant_nf4_segment(uint64_t n, uint64_t block, int absmax_es, int j, uint64_t* out);
+// MXFP4 (OCP microscaling: e2m1 elements, one e8m0 scale byte per block of 32) expansion in place
+// (csrc/kernels/dequant.hip; flexible_llm_sharding_amd/mxfp4.py holds the definition and the landing
+// layout, region_layout()).  region: the tensor's 2n-byte image region (2-byte aligned) in which the
+// n / 2 packed bytes (low nibble first) and the n / 32 scale bytes have landed segment by segment;
+// afterwards it holds n fp16 values, w16[i] = fp16_rne(e2m1(nibble(i)) * 2^(e[i / 32] - 127)), the
+// product exact and rounded once, 0x7E00 where e = 255.  Uses no other device memory and no tables:
+// fls_dequant_mxfp4_launches(n) stream-ordered launches on s, the last a single block of at most
+// fls_dequant_mxfp4_tail() weights.  hipErrorInvalidValue, with nothing launched, for a missing
+// pointer, an odd region address or n % 32 != 0; n == 0 returns 0.
+int fls_dequant_mxfp4(void* region, uint64_t n, fls_stream_t s);
+int fls_dequant_mxfp4_launches(uint64_t n);
+int fls_dequant_mxfp4_tail(void);
+// launch j of that chain: out[6] = {a, b, packed offset, scale offset, first block, blocks} (host only)
+int fls_dequant_mxfp4_segment(uint64_t n, int j, uint64_t* out);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0
 int fls_gemv_skinny(const void* x, const void* w, void* c, int M, int N, int K, int ldx, int ldw, int ldc,
                     fls_stream_t s);

@@ -542,3 +542,172 @@ extern "C" int fls_dequant_nf4(void* region, uint64_t n, uint64_t block, int abs
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// MXFP4 (OCP microscaling: e2m1 elements, one e8m0 scale byte per 32) expansion in place
+// (flexible_llm_sharding_amd/mxfp4.py holds the definition; the landing layout is INT4's above with
+// groups of 32 and one-byte scales, so every segment boundary is a block boundary and no launch reads
+// a scale of another segment).
+//
+//   w16[i] = fp16_rne( e2m1(nibble(i)) * 2^(e[i / 32] - 127) ),   0x7E00 for e = 255
+//
+// the product exact, rounded once.  Byte j of the packed stream holds element 2j in its LOW nibble.
+// What is left shrinks by 1 / (1/4 + 1/64) = 3.76 per launch: 9 launches for 8192 x 28672.  There is
+// no table, no LDS and no fp32 arithmetic on the data path.
+//
+// One thread owns one MX block: one 16-byte load of its 32 nibbles, its scale byte, 16
+// v_cvt_scalef32_pk_f16_fp4 (four dwords x four op_sel byte selects), four 16-byte stores.
+//   * The instruction takes byte `sel` of the source dword and returns two fp16: the LOW nibble in
+//     bits [15:0], the high nibble in bits [31:16].  Byte sel of dword j holds elements 8j + 2 sel and
+//     8j + 2 sel + 1, so result (j, sel) IS dword 4j + sel of the thread's 64 output bytes, in store
+//     order, with nothing to shuffle: store j writes results (j, 0..3).
+//   * The scale operand is the fp32 with bits e << 23, i.e. 2^(e - 127), made by one shift.
+//   * A wave's 64 scale bytes are contiguous (kThreads % 64 == 0: no wave spans two thread blocks)
+//     and, the segment's scales starting 16-byte aligned and a wave's first block being a multiple
+//     of 64, dword aligned: lanes 0..15 load them as 16 dwords
+//     (lane L the scales of lanes 4L .. 4L + 3; a dword that starts past the last block is not
+//     loaded, one that ends past it reads at most 3 bytes of the segment's own packed bytes), one
+//     ds_bpermute hands lane L the dword of lane L / 4, a shift and a mask select its byte.
+//   * The hardware convert is used only where it was measured equal to the definition
+//     (scripts/mxfp4_probe.py on an MI355X, profiles/mxfp4/README.md): for e in 0 .. 254 the
+//     instruction gives the definition's bits for all 16 nibbles, every byte select and both halves:
+//     the subnormal ties, overflow to +-inf, -0, and +-0 for e = 0 (operand bits 0) included.  It
+//     differs for e = 255 alone, where it returns 0xFE00 and the definition is 0x7E00.  A block with
+//     e = 255 takes a per-thread branch that writes the NaN pattern; no checkpoint holds one on
+//     purpose, so waves do not diverge in practice.
+// A region base that is not 16-byte aligned takes the same schedule with scalar loads and stores.
+namespace {
+
+constexpr int kMxBlock = 32;
+static_assert(kThreads % 64 == 0, "a wave's 64 blocks, and so its scale bytes, must be consecutive");
+
+typedef _Float16 mx_half2 __attribute__((ext_vector_type(2)));
+
+template <int SEL>
+__device__ __forceinline__ uint32_t mx_cvt(uint32_t w, float sc) {
+  return __builtin_bit_cast(uint32_t, (mx_half2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, SEL));
+}
+
+// this launch expands elements [a, a + cnt), a % 32 == cnt % 32 == 0: block t of the launch has its
+// nibbles at byte p_off + 16 t and its scale at byte s_off + t.  TAIL: one block, cnt <= kTail4, every
+// read completes before any write (the ranges overlap).
+template <bool VEC, bool TAIL>
+__global__ __launch_bounds__(kThreads) void dequant_mxfp4_kernel(uint8_t* region, uint64_t a, uint64_t cnt,
+                                                                 uint64_t p_off, uint64_t s_off) {
+  const uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  const uint64_t nblk = cnt / kMxBlock;
+  const bool active = t < nblk;
+  int e = 0;
+  if (VEC) {      // (every lane of the wave takes part in the exchange: before any lane leaves)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t d = t - lane + 4 * lane;      // the wave's first block + 4 lane
+    uint32_t sw = 0u;
+    if (lane < 16u && d < nblk) sw = *(const uint32_t*)(region + s_off + d);
+    sw = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane >> 2) << 2), (int)sw);
+    e = (int)((sw >> (8u * (lane & 3u))) & 255u);
+  } else if (active) {
+    e = region[s_off + t];
+  }
+  if (!TAIL && !active) return;
+  uint32_t o[16];
+  if (active) {
+    uint32_t w[4];
+    const uint8_t* src = region + p_off + t * 16;
+    if (VEC) {
+      const uint4 v = *(const uint4*)src;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) |
+               ((uint32_t)src[4 * j + 3] << 24);
+    }
+    if (e != 255) {
+      const float sc = __uint_as_float((uint32_t)e << 23);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o[4 * j] = mx_cvt<0>(w[j], sc);
+        o[4 * j + 1] = mx_cvt<1>(w[j], sc);
+        o[4 * j + 2] = mx_cvt<2>(w[j], sc);
+        o[4 * j + 3] = mx_cvt<3>(w[j], sc);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) o[j] = 0x7E007E00u;      // the format's NaN, twice
+    }
+  }
+  if (TAIL) __syncthreads();
+  if (!active) return;
+  uint8_t* dst = region + 2 * (a + t * kMxBlock);
+  if (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *(uint4*)(dst + 16 * j) = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      *(uint16_t*)(dst + 4 * j) = (uint16_t)o[j];
+      *(uint16_t*)(dst + 4 * j + 2) = (uint16_t)(o[j] >> 16);
+    }
+  }
+}
+
+inline bool argsmx_ok(uint64_t n) { return n % kMxBlock == 0 && n < (1ull << 60); }
+
+}  // namespace
+
+extern "C" int fls_dequant_mxfp4_tail(void) { return kTail4; }
+
+// launches fls_dequant_mxfp4 enqueues for a tensor of n weights (-1: bad arguments)
+extern "C" int fls_dequant_mxfp4_launches(uint64_t n) {
+  if (!argsmx_ok(n)) return -1;
+  if (n == 0) return 0;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, kMxBlock, 1, segs);
+  return c > 0 ? c : -1;
+}
+
+// launch j (0 .. launches - 1) of that chain, for tests of the mirror: out = {a, b, packed offset,
+// scale offset, first block, blocks}.  0, or -1 for bad arguments or j
+extern "C" int fls_dequant_mxfp4_segment(uint64_t n, int j, uint64_t* out) {
+  if (!out || n == 0 || !argsmx_ok(n)) return -1;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, kMxBlock, 1, segs);
+  if (c <= 0 || j < 0 || j >= c) return -1;
+  const Seg4& s = segs[c - 1 - j];
+  out[0] = s.a; out[1] = s.b; out[2] = s.p_off; out[3] = s.s_off; out[4] = s.k0; out[5] = s.ng;
+  return 0;
+}
+
+extern "C" int fls_dequant_mxfp4(void* region, uint64_t n, fls_stream_t s) {
+  if (n == 0) return 0;
+  if (!region || ((uintptr_t)region & 1) || !argsmx_ok(n)) return (int)hipErrorInvalidValue;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, kMxBlock, 1, segs);
+  if (c <= 0) return (int)hipErrorInvalidValue;
+  const bool vec = ((uintptr_t)region & 15) == 0;
+  auto st = (hipStream_t)s;
+  auto* r = (uint8_t*)region;
+  for (int j = c - 1; j >= 0; --j) {      // launch order: from the bottom segment to the tail
+    const Seg4& g4 = segs[j];
+    const uint64_t cnt = g4.b - g4.a;
+    const uint64_t blocks = (cnt / kMxBlock + kThreads - 1) / kThreads;
+    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    if (j == 0) {      // cnt <= kTail4: one block
+      if (vec)
+        hipLaunchKernelGGL((dequant_mxfp4_kernel<true, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off);
+      else
+        hipLaunchKernelGGL((dequant_mxfp4_kernel<false, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off);
+    } else {
+      if (vec)
+        hipLaunchKernelGGL((dequant_mxfp4_kernel<true, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off);
+      else
+        hipLaunchKernelGGL((dequant_mxfp4_kernel<false, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off);
+    }
+    FLS_CHECK_LAUNCH();
+  }
+  return 0;
+}

@@ -111,7 +111,7 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device, lora=
         return HostStore.synthetic(cfg, device, seed=0, pinned=device.type == "cuda", names=mine, fold_norms=fold)
     src = FileLayerSource(cfg, args.model_path, names=mine, direct=getattr(args, "o_direct", False))
     tensors = src.tensors()                # (every layer's plan is made now: a bad file is refused here)
-    for f in quant.FORMATS:
+    for f in quant.ALL_FORMATS:
         if tensors[f.name] and getattr(args, "verbose", False):
             print(f.verbose.format(n=tensors[f.name], ignored=len(src.ignored_scales())), file=sys.stderr)
     if resolve_weight_cache(args, cfg, comm, mine, sliced=False, source=src) == "stream":
@@ -136,7 +136,7 @@ def check_fp8_dp_shard(args, cfg: ModelConfig) -> None:
     names = mode_layer_names(cfg, getattr(args, "score_mode", "next_token"))
     src = FileLayerSource(cfg, args.model_path, names=names)
     tensors = src.tensors()
-    for f in reversed(quant.FORMATS):
+    for f in reversed(quant.ALL_FORMATS):
         if tensors[f.name]:
             raise ValueError(f"--dp_weight_shard true does not serve an {f.label} checkpoint (its 1/G byte slices cut "
                              "through tensors): pass --dp_weight_shard false, or run model parallel")
@@ -688,7 +688,7 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     metrics["weight_file_bytes"] = int(files.file_bytes() if hasattr(files, "file_bytes")
                                        else getattr(src, "total_bytes", 0))
     tensors = files.tensors() if hasattr(files, "tensors") else {}
-    metrics.update({f"{f.name}_tensors": int(tensors.get(f.name, 0)) for f in quant.FORMATS})
+    metrics.update({f"{f.name}_tensors": int(tensors.get(f.name, 0)) for f in quant.ALL_FORMATS})
     ad = getattr(runner, "lora", None)
     metrics.update({"lora_tensors": int(ad.n_tensors) if ad else 0, "lora_rank_max": int(ad.rank_max) if ad else 0,
                     "lora_bytes": int(ad.nbytes) if ad else 0, "lora_merge_launches": int(ad.merge_launches) if ad else 0})

@@ -762,6 +762,15 @@ class HipOps:
                                     nested_block if u8 else 0, float(offset) if u8 else 0.0, _stream()),
              "fls_dequant_nf4")
 
+    def dequant_mxfp4(self, region: torch.Tensor, numel: int) -> None:
+        """Expand the MXFP4 tensor of ``numel`` weights that landed in its ``2 * numel``-byte ``region``
+        (mxfp4.region_layout) to fp16 in place (mxfp4.py's definition; csrc/kernels/dequant.hip)."""
+        if region.numel() * region.element_size() != 2 * numel or not region.is_contiguous():
+            raise ValueError("the region of an MXFP4 tensor is 2 bytes per weight")
+        if numel % 32:
+            raise ValueError(f"the {numel} weights of an MXFP4 tensor are no whole blocks of 32")
+        _chk(self.k.fls_dequant_mxfp4(region.data_ptr(), numel, _stream()), "fls_dequant_mxfp4")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -386,6 +386,20 @@ class TorchOps:
                            code2, nested_absmax, nested_block, offset)
         b.view(torch.float16).copy_(w.reshape(-1))
 
+    def dequant_mxfp4(self, region: torch.Tensor, numel: int) -> None:
+        """The MXFP4 tensor of ``numel`` weights that landed in its ``2 * numel``-byte ``region``
+        (mxfp4.region_layout) -> fp16 in place, by the host definition (mxfp4.dequantize)."""
+        from .. import mxfp4
+        b = region.view(torch.uint8)
+        if b.numel() != 2 * numel:
+            raise ValueError("the region of an MXFP4 tensor is 2 bytes per weight")
+        if numel == 0:
+            return
+        packed, scales = mxfp4.unland(b.to("cpu"), numel, mxfp4.BLOCK, mxfp4.SCALE_ES)
+        rows = numel // mxfp4.BLOCK                # (one row per block: the value depends on nothing else)
+        w = mxfp4.dequantize(packed.view(rows, mxfp4.BLOCK // 2), scales.view(rows, 1), (rows, mxfp4.BLOCK))
+        b.view(torch.float16).copy_(w.reshape(-1))
+
     # ------------------------------------------------------- synthetic init
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         """Random-init one packed layer in place (norm weights ~ 1, embeddings ~ N(0,1))."""

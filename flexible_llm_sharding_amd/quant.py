@@ -1,8 +1,8 @@
 """What the weight-only checkpoint formats share: the format table, the 4-bit landing layout, the
 twin writer, the ``--quantize`` dispatch and the checkpoint-name lookups of the loader.
 
-The formats themselves (value definition, converter, checks) are :mod:`.fp8`, :mod:`.int4` and
-:mod:`.nf4`; the device kernels are ``csrc/kernels/dequant.hip``.
+The formats themselves (value definition, converter, checks) are :mod:`.fp8`, :mod:`.int4`,
+:mod:`.nf4` and :mod:`.mxfp4`; the device kernels are ``csrc/kernels/dequant.hip``.
 
 Landing layout of a 4-bit tensor (:func:`segments`).  A tensor of ``N`` weights owns its ``2N``-byte
 region of the layer image and nothing else.  The kernel expands elements ``[a, b)`` per stream-ordered
@@ -56,7 +56,7 @@ def segments(n: int, g: int, scale_es: int) -> Tuple[Segment, ...]:
     """The segments of a tensor of ``n`` weights in groups of ``g`` with ``scale_es``-byte scales, in
     launch order.  Built from the top of the ``2n``-byte region: the tail first, then each earlier
     launch as large as ``2 b <= scale_off`` allows.  The arguments are the caller's to check
-    (``int4.region_layout``, ``nf4.region_layout``)."""
+    (``int4.region_layout``, ``nf4.region_layout``, ``mxfp4.region_layout``)."""
     segs: List[Segment] = []
     if n == 0:
         return ()
@@ -131,7 +131,7 @@ def write_twin(src_dir: str, dst_dir: str, dequantize_state_dict) -> None:
 
 
 # --------------------------------------------------------------------------- the format table
-from . import fp8, int4, nf4          # noqa: E402  (int4 and nf4 import the landing layout above)
+from . import fp8, int4, mxfp4, nf4   # noqa: E402  (the 4-bit modules import the landing layout above)
 
 
 class Format(NamedTuple):
@@ -149,13 +149,22 @@ FORMATS = (
 )
 BY_NAME = {f.name: f for f in FORMATS}
 SEGMENTED = ("int4", "nf4")           # the 4-bit formats: they land segment by segment
+# FORMATS, BY_NAME and SEGMENTED are frozen at the three formats above: tests/test_quant_cpu.py pins
+# them entry for entry and lines them up with fixed tuples such as ``(is_fp8, is_int4, is_nf4)``.
+# Nothing in the package reads them any more and new code MUST NOT: it would miss every format added
+# since.  The tables below are the ones the loader, the converter and the metrics go through.
+ALL_FORMATS = FORMATS + (
+    Format("mxfp4", "MXFP4", mxfp4, "MXFP4 checkpoint: {n} e2m1 tensors with e8m0 block scales are expanded to fp16 in HBM"),
+)
+FORMAT_BY_NAME = {f.name: f for f in ALL_FORMATS}
+LANDS_SEGMENTED = SEGMENTED + ("mxfp4",)
 
 
 def quantize_format(quantize: str) -> Format:
     """The format ``--quantize`` names; ValueError otherwise."""
-    if quantize not in BY_NAME:
-        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4")
-    return BY_NAME[quantize]
+    if quantize not in FORMAT_BY_NAME:
+        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4, or mxfp4")
+    return FORMAT_BY_NAME[quantize]
 
 
 def quantize_state_dict(sd: Dict[str, torch.Tensor], quantize: str, fp8_scale: str = "channel",
@@ -164,15 +173,16 @@ def quantize_state_dict(sd: Dict[str, torch.Tensor], quantize: str, fp8_scale: s
     """``--quantize`` of one file's tensors: the named format's own ``quantize_state_dict`` with its
     own options."""
     args = {"fp8": (fp8_scale,), "int4": (int4_group, int4_scale_dtype), "nf4": (nf4_block, nf4_double_quant)}
-    return quantize_format(quantize).module.quantize_state_dict(sd, *args[quantize])
+    return quantize_format(quantize).module.quantize_state_dict(sd, *args.get(quantize, ()))
 
 
 # --------------------------------------------------------------------------- checkpoint names
 def is_companion(name: str, want) -> bool:
     """``name`` belongs to a weight among ``want`` in some format: an FP8 scale, the words, scales or
-    shape of an INT4 weight, the absmax, code books or quant state of a bitsandbytes 4-bit weight."""
+    shape of an INT4 weight, the absmax, code books or quant state of a bitsandbytes 4-bit weight, the
+    block scales of an MXFP4 weight."""
     return ((fp8.is_scale_name(name) and fp8.weight_of_scale(name) in want)
-            or any(m.is_companion_name(name) and m.weight_of_companion(name) in want for m in (int4, nf4)))
+            or any(m.is_companion_name(name) and m.weight_of_companion(name) in want for m in (int4, nf4, mxfp4)))
 
 
 def source(weight_name: str, infos, where: str = "") -> Tuple[Optional[str], Optional[str]]:
@@ -187,4 +197,6 @@ def source(weight_name: str, infos, where: str = "") -> Tuple[Optional[str], Opt
                         "holds one of the two")
     if nf4.is_nf4_source(weight_name, infos):
         return "nf4", weight_name
+    if mxfp4.is_mxfp4_source(weight_name, infos):
+        return "mxfp4", weight_name
     return ("fp8" if infos[weight_name].dtype == fp8.FP8_DTYPE else None), weight_name

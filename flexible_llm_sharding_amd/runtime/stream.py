@@ -26,6 +26,7 @@ Here the same small-RAM envelope costs no CPU work per pass:
   (:mod:`..int4`) and bitsandbytes 4-bit (:mod:`..nf4`): nibbles and raw scale (absmax) bytes,
   segment by segment into the top of the region (the landing layout of :mod:`..quant`); the scales
   travel with the weights, NF4's small tables (code books, nested absmax) are read at plan time.
+  MXFP4 (:mod:`..mxfp4`) lands the same way, with blocks of 32 and one-byte scales and no tables.
   What is read at plan time is resident on the device in one arena per source
   (:meth:`FileLayerSource.prepare_device`).
 
@@ -46,7 +47,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, fp8, int4, knobs, nf4, quant
+from .. import _native, fp8, int4, knobs, mxfp4, nf4, quant
 from ..config import ModelConfig
 from ..models.layout import check_layer_tensors, layer_kind, layer_layout, placements, source_key
 from ..ops import get_ops
@@ -64,7 +65,7 @@ class TensorRun:
     """One checkpoint tensor: file bytes at ``file_off`` -> image bytes [img_off, img_off + 2 * numel).
 
     A plain tensor (``fmt`` None: fp16 / bf16 / fp32) is ``numel * src_es`` file bytes; any part of it
-    loads on its own.  A quantised tensor (``fmt`` a name of ``quant.FORMATS``) loads whole: its file
+    loads on its own.  A quantised tensor (``fmt`` a name of ``quant.ALL_FORMATS``) loads whole: its file
     bytes land inside its own region and :meth:`expand` turns them into fp16 in place there.
     ``tables`` are its small operands that do not travel with the weights, read at plan time and
     kept as host tensors; the first ``books`` of them are code books, of which a source's device
@@ -81,7 +82,11 @@ class TensorRun:
     ``"nf4"`` (bitsandbytes 4-bit, :mod:`..nf4`): ``numel / 2`` packed bytes at ``file_off`` plus
     ``numel / group`` raw absmax entries (``group`` is the block size, ``scale_dtype`` U8 or F32) at
     ``scale_off``, landing as ``nf4.region_layout`` lays them out; ``quant`` holds the checked quant
-    state, ``tables`` is its ``(code, code2, nested_absmax)``."""
+    state, ``tables`` is its ``(code, code2, nested_absmax)``.
+
+    ``"mxfp4"`` (:mod:`..mxfp4`): ``numel / 2`` packed bytes at ``file_off`` plus ``numel / 32`` e8m0
+    scale bytes (``group`` 32, ``scale_dtype`` U8) at ``scale_off``, landing as ``mxfp4.region_layout``
+    lays them out.  No tables."""
     hf_name: str
     file_off: int
     img_off: int
@@ -114,9 +119,13 @@ class TensorRun:
         return self.fmt == "nf4"
 
     @property
+    def is_mxfp4(self) -> bool:
+        return self.fmt == "mxfp4"
+
+    @property
     def lands_segmented(self) -> bool:
-        """A 4-bit tensor (INT4 or NF4): it lands segment by segment."""
-        return self.fmt in quant.SEGMENTED
+        """A 4-bit tensor (INT4, NF4 or MXFP4): it lands segment by segment."""
+        return self.fmt in quant.LANDS_SEGMENTED
 
     @property
     def scale_es(self) -> int:
@@ -138,7 +147,7 @@ class TensorRun:
         """(file_off, bytes, region offset) of a 4-bit tensor's landing pieces: per segment its packed
         bytes and, where it holds any, the raw scale bytes of the groups that end in it."""
         out = []
-        for s in quant.BY_NAME[self.fmt].module.region_layout(self.numel, self.group, self.scale_es):
+        for s in quant.FORMAT_BY_NAME[self.fmt].module.region_layout(self.numel, self.group, self.scale_es):
             if s.n_groups:
                 out.append((self.scale_off + s.first_group * self.scale_es, s.n_groups * self.scale_es, s.scale_off))
             out.append((self.file_off + s.a // 2, (s.b - s.a) // 2, s.packed_off))
@@ -146,7 +155,7 @@ class TensorRun:
 
     def landing_span(self) -> Tuple[int, int]:
         """``(offset, bytes)`` of the part of a 4-bit tensor's region that its landed inputs occupy."""
-        return quant.BY_NAME[self.fmt].module.landing_span(self.numel, self.group, self.scale_es)
+        return quant.FORMAT_BY_NAME[self.fmt].module.landing_span(self.numel, self.group, self.scale_es)
 
     def expand(self, ops, region: torch.Tensor, tables: Sequence[Optional[torch.Tensor]]) -> None:
         """Expand the landed tensor to fp16 in place in its ``2 * numel``-byte ``region`` through
@@ -156,6 +165,8 @@ class TensorRun:
             ops.dequant_fp8(region, self.numel, *tables, self.scale_kind, self.cols)
         elif self.fmt == "int4":
             ops.dequant_int4(region, self.numel, self.group, self.scale_dtype)
+        elif self.fmt == "mxfp4":
+            ops.dequant_mxfp4(region, self.numel)
         else:
             q = self.quant
             ops.dequant_nf4(region, self.numel, q.block, q.absmax_kind, *tables, q.nested_block, q.offset)
@@ -175,7 +186,7 @@ class LayerPlan:
         for pl in placements(cfg, layer_name):
             key = source_key(cfg, layer_name, pl.hf_name, infos)
             fmt = quant.source(pl.hf_name, infos)[0]
-            if fmt in quant.SEGMENTED:
+            if fmt in quant.LANDS_SEGMENTED:
                 runs.append(getattr(self, f"_{fmt}_run")(path, pl, infos))
                 continue
             ti: TensorInfo = infos[key]
@@ -204,6 +215,7 @@ class LayerPlan:
     fp8_tensors = property(lambda self: self.tensors["fp8"])
     int4_tensors = property(lambda self: self.tensors["int4"])
     nf4_tensors = property(lambda self: self.tensors["nf4"])
+    mxfp4_tensors = property(lambda self: self.tensors["mxfp4"])
 
     @staticmethod
     def _fp8_run(path: str, key: str, ti: TensorInfo, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
@@ -258,6 +270,17 @@ class LayerPlan:
                          (qs.code, qs.code2, qs.nested_absmax), books=2, group=qs.block, scale_off=ai.begin,
                          scale_dtype=ai.dtype, quant=qs)
 
+    @staticmethod
+    def _mxfp4_run(path: str, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
+        """The run of the MXFP4 tensor that feeds placement ``pl``.  Nothing is read now: the scale
+        bytes are read with the weights, every pass."""
+        pk, sk = mxfp4.check_entry(pl.hf_name, infos, pl.shape, f"{path}: ")
+        ti, si = infos[pk], infos[sk]
+        if ti.nbytes != pl.numel // 2 or si.nbytes != pl.numel // mxfp4.BLOCK:
+            raise ValueError(f"{path}: {pk} / {sk} byte sizes do not match their shapes")
+        return TensorRun(pl.hf_name, ti.begin, pl.offset, pl.numel, ti.dtype, "mxfp4", group=mxfp4.BLOCK,
+                         scale_off=si.begin, scale_dtype=si.dtype)
+
     def pieces(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
         """(file_off, file_bytes, dst_off, kind) covering image bytes [lo, hi); dst_off relative to lo.
         lo / hi must be even (whole fp16 elements)."""
@@ -270,7 +293,7 @@ class LayerPlan:
             if a >= b:
                 continue
             if r.fmt and (a, b) != (r.img_off, r.img_off + 2 * r.numel):
-                label = quant.BY_NAME[r.fmt].label
+                label = quant.FORMAT_BY_NAME[r.fmt].label
                 raise ValueError(f"{self.path}: image range [{lo}, {hi}) cuts through the {label} tensor "
                                  f"{r.hf_name} (an {label} tensor loads whole)")
             if r.lands_segmented:
@@ -542,6 +565,9 @@ class FileLayerSource(LayerSource):
 
     def nf4_tensors(self) -> int:
         return self.tensors()["nf4"]
+
+    def mxfp4_tensors(self) -> int:
+        return self.tensors()["mxfp4"]
 
     def file_bytes(self, names: Optional[Sequence[str]] = None) -> int:
         """Tensor bytes of the layer files (what a pass reads and copies)."""

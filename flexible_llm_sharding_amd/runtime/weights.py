@@ -17,7 +17,7 @@ Here a source yields the *packed* layer image (see :mod:`..models.layout`):
   weights (generated on the GPU and copied down) for the 70B benchmark.
 * :class:`CompactHostStore` — a quantised checkpoint's file bytes resident in
   pinned host memory as they are in the files (FP8: half the RAM and PCIe bytes
-  of the fp16 image; INT4 and NF4: about a quarter), copied tensor by tensor to
+  of the fp16 image; INT4, NF4 and MXFP4: about a quarter), copied tensor by tensor to
   their landing positions and expanded to fp16 in the HBM slot as the file
   source does (:mod:`.stream` describes where each format lands).
 * data-parallel scatter-load (:func:`piece_slices`): a rank keeps only its
@@ -264,7 +264,7 @@ class CompactHostStore(LayerSource):
     False: norms cannot be folded into quantised bytes without requantising, so they are folded as
     each layer lands.
 
-    A 4-bit tensor (``TensorRun.lands_segmented``: INT4, NF4) is pinned as its landing image: the
+    A 4-bit tensor (``TensorRun.lands_segmented``: INT4, NF4, MXFP4) is pinned as its landing image: the
     packed bytes and raw scales of its segments in the order and at the offsets they take in the
     tensor's region (the landing layout of :mod:`..quant`), so the whole tensor is still one H2D
     (``TensorRun.landing_span``)."""
@@ -325,7 +325,7 @@ class CompactHostStore(LayerSource):
         return self.files.plan(name)
 
     def fold_norms(self, device):
-        raise ValueError("--weight_cache host keeps an FP8, INT4 or NF4 checkpoint's bytes as they are in the files: norms "
+        raise ValueError("--weight_cache host keeps an FP8, INT4, NF4 or MXFP4 checkpoint's bytes as they are in the files: norms "
                          "cannot be folded into quantised weights (they are folded as each layer lands)")
 
     def read_into(self, name: str, dst: torch.Tensor) -> None:

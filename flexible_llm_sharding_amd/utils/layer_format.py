@@ -113,7 +113,9 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
     ``int4_scale_dtype`` scales (int4.quantize_state_dict).  A bitsandbytes 4-bit source checkpoint
     passes through with its bytes unchanged, the companions of a weight (``X.weight.absmax``,
     ``.quant_map``, ``.nested_*``, ``.quant_state.bitsandbytes__nf4``) in its layer file;
-    ``quantize="nf4"`` writes that form from float weights (nf4.quantize_state_dict)."""
+    ``quantize="nf4"`` writes that form from float weights (nf4.quantize_state_dict).  An MXFP4
+    source checkpoint (U8 ``weight`` and U8 ``weight_scale``) passes through with its bytes unchanged;
+    ``quantize="mxfp4"`` writes that form from float weights (mxfp4.quantize_state_dict)."""
     if quantize is not None:
         quant.quantize_format(quantize)         # (an unknown name is refused before anything is written)
     os.makedirs(out_dir, exist_ok=True)

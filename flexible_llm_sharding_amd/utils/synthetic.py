@@ -118,7 +118,8 @@ def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
     ``fp8_scale`` (channel | tensor | block128) scales (fp8.quantize_state_dict); ``quantize="int4"``:
     as INT4 words in groups of ``int4_group`` with ``int4_scale_dtype`` scales (int4.quantize_state_dict);
     ``quantize="nf4"``: in the bitsandbytes 4-bit form, NF4 code book, blocks of ``nf4_block``, the
-    absmax 8-bit quantised if ``nf4_double_quant`` (nf4.quantize_state_dict).
+    absmax 8-bit quantised if ``nf4_double_quant`` (nf4.quantize_state_dict).  ``quantize="mxfp4"``:
+    as OCP MXFP4, e2m1 bytes with one e8m0 scale per 32 weights (mxfp4.quantize_state_dict).
     ``unique_layers`` > 0: only the first K decoder layers get their own random weights;
     decoder layer i >= K is a hard link to layer i % K (a 138 GB 70B checkpoint in ~K x 1.7 GB of
     disk for streaming benchmarks — the reads are per file, as for a real checkpoint)."""
