@@ -267,6 +267,25 @@ int fls_dequant_mxfp4_launches(uint64_t n);
 int fls_dequant_mxfp4_tail(void);
 // launch j of that chain: out[6] = {a, b, packed offset, scale offset, first block, blocks} (host only)
 int fls_dequant_mxfp4_segment(uint64_t n, int j, uint64_t* out);
+// GPTQ / AWQ 4-bit checkpoints (flexible_llm_sharding_amd/gptq.py holds the layouts and the value).
+// region: the 2 * out * in-byte image region (2-byte aligned) of an [out, in] weight at whose bottom the
+// file's qweight, scales and qzeros have landed contiguously (fls_repack_w4_input: o[4] = {qweight,
+// scales, qzeros offset, end}).  fls_repack_w4 (csrc/kernels/repack.hip; layout 0 GPTQ, 1 AWQ GEMM)
+// transposes them in one launch into INT4's segmented landing layout at the top of the region: the
+// nibbles row-major [out, in] and one 4-byte entry (fp16 scale, u16 zero point) per group.
+// fls_dequant_w4z (csrc/kernels/dequant.hip) then expands those segments in place,
+// w16[i] = fp16_rne(fp32(nibble(i) - z[i / group]) * fp32(s[i / group])), in
+// fls_dequant_w4z_launches(n, group) stream-ordered launches, the last a single block of at most
+// fls_dequant_w4z_tail() weights.  Neither uses other device memory.  hipErrorInvalidValue, with
+// nothing launched, for a missing pointer, an odd region address, out % 8 != 0, in % 32 != 0,
+// group % 32 != 0, in % group != 0 (n % group != 0) or an unknown layout; no weights: returns 0.
+int fls_repack_w4(void* region, uint64_t out, uint64_t in, uint64_t group, int layout, fls_stream_t s);
+int fls_repack_w4_input(uint64_t out, uint64_t in, uint64_t group, uint64_t* o);
+int fls_dequant_w4z(void* region, uint64_t n, uint64_t group, fls_stream_t s);
+int fls_dequant_w4z_launches(uint64_t n, uint64_t group);
+int fls_dequant_w4z_tail(void);
+// launch j of that chain: out[6] = {a, b, packed offset, entry offset, first group, groups} (host only)
+int fls_dequant_w4z_segment(uint64_t n, uint64_t group, int j, uint64_t* out);
 // C[M,N] = X[M,K] W[N,K]^T for M <= 16 (skinny LM head); K % 32 == 0
 int fls_gemv_skinny(const void* x, const void* w, void* c, int M, int N, int K, int ldx, int ldw, int ldc,
                     fls_stream_t s);

@@ -368,6 +368,144 @@ extern "C" int fls_dequant_int4(void* region, uint64_t n, uint64_t group, int sc
 }
 
 // ---------------------------------------------------------------------------------------------
+// 4-bit with zero points (GPTQ / AWQ after fls_repack_w4, csrc/kernels/repack.hip;
+// flexible_llm_sharding_amd/gptq.py holds the definition): INT4's in-place chain above over the same
+// segments with 4-byte group entries, the fp16 scale in the low half and the zero point 0..15 in the
+// high half.
+//
+//   w16[i] = fp16_rne( fp32(nibble(i) - z[i / g]) * fp32(s[i / g]) )
+//
+// Each thread expands 32 weights of one group: one 16-byte load of nibbles, its entry read once
+// (one dword), nibble - z -> fp32, a plain fp32 multiply, v_cvt_f16_f32, four 16-byte stores.  The
+// first launch overwrites the file tensors at the bottom of the region, which are dead once the
+// repack, ordered before it on the stream, has run.
+namespace {
+
+template <bool VEC>
+__device__ __forceinline__ uint32_t load_entry(const uint8_t* region, uint64_t off, uint64_t idx) {
+  const uint8_t* p = region + off + idx * 4;
+  if (VEC) return *(const uint32_t*)p;
+  return (uint32_t)*(const uint16_t*)p | ((uint32_t)*(const uint16_t*)(p + 2) << 16);
+}
+
+// as dequant_int4_kernel: elements [a, a + cnt), nibbles at p_off, the entries of groups [k0, k_next)
+// at s_off, that of group k_next (the one that straddles a + cnt) at s_next
+template <bool VEC, bool TAIL>
+__global__ __launch_bounds__(kThreads) void dequant_w4z_kernel(uint8_t* region, uint64_t a, uint64_t cnt,
+                                                               uint64_t p_off, uint64_t s_off, uint64_t k0,
+                                                               uint64_t k_next, uint64_t s_next, uint64_t g) {
+  const uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  const uint64_t off = t * kPer4;
+  const bool active = off < cnt;
+  if (!TAIL && !active) return;
+  half_t o[kPer4];
+  if (active) {
+    uint32_t w[4];
+    const uint8_t* src = region + p_off + off / 2;
+    if (VEC) {
+      const uint4 v = *(const uint4*)src;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[j] = (uint32_t)*(const uint16_t*)(src + 4 * j) | ((uint32_t)*(const uint16_t*)(src + 4 * j + 2) << 16);
+    }
+    const uint64_t k = (a + off) / g;
+    const uint32_t e = k < k_next ? load_entry<VEC>(region, s_off, k - k0) : load_entry<VEC>(region, s_next, 0);
+    const float s = (float)__builtin_bit_cast(half_t, (uint16_t)e);
+    const int z = (int)(e >> 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const int q = (int)((w[j] >> (4 * b)) & 15u) - z;
+        o[8 * j + b] = to_half((float)q * s);
+      }
+  }
+  if (TAIL) __syncthreads();
+  if (!active) return;
+  half_t* dst = (half_t*)region + a + off;
+  if (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      half8 v;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) v[b] = o[8 * j + b];
+      *(half8*)(dst + 8 * j) = v;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kPer4; ++j) dst[j] = o[j];
+  }
+}
+
+constexpr uint64_t kEntryW4z = 4;      // bytes of a group entry
+
+}  // namespace
+
+extern "C" int fls_dequant_w4z_tail(void) { return kTail4; }
+
+// launches fls_dequant_w4z enqueues for a tensor of n weights in groups of `group` (-1: bad arguments)
+extern "C" int fls_dequant_w4z_launches(uint64_t n, uint64_t group) {
+  if (!args4_ok(n, group, (int)kEntryW4z)) return -1;
+  if (n == 0) return 0;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, kEntryW4z, segs);
+  return c > 0 ? c : -1;
+}
+
+// launch j (0 .. launches - 1) of that chain: out = {a, b, packed offset, entry offset, first group,
+// groups}.  0, or -1 for bad arguments or j
+extern "C" int fls_dequant_w4z_segment(uint64_t n, uint64_t group, int j, uint64_t* out) {
+  if (!out || n == 0 || !args4_ok(n, group, (int)kEntryW4z)) return -1;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, kEntryW4z, segs);
+  if (c <= 0 || j < 0 || j >= c) return -1;
+  const Seg4& s = segs[c - 1 - j];
+  out[0] = s.a; out[1] = s.b; out[2] = s.p_off; out[3] = s.s_off; out[4] = s.k0; out[5] = s.ng;
+  return 0;
+}
+
+extern "C" int fls_dequant_w4z(void* region, uint64_t n, uint64_t group, fls_stream_t s) {
+  if (n == 0) return 0;
+  if (!region || ((uintptr_t)region & 1)) return (int)hipErrorInvalidValue;
+  if (!args4_ok(n, group, (int)kEntryW4z)) return (int)hipErrorInvalidValue;
+  Seg4 segs[kMaxSeg4];
+  const int c = layout4(n, group, kEntryW4z, segs);
+  if (c <= 0) return (int)hipErrorInvalidValue;
+  const bool vec = ((uintptr_t)region & 15) == 0;
+  auto st = (hipStream_t)s;
+  auto* r = (uint8_t*)region;
+  for (int j = c - 1; j >= 0; --j) {      // launch order: from the bottom segment to the tail
+    const Seg4& g4 = segs[j];
+    // the straddling group g4.b / group: the first entry of the next segment (towards the tail) that has any
+    uint64_t s_next = 0;
+    for (int i = j - 1; i >= 0; --i)
+      if (segs[i].ng) { s_next = segs[i].s_off; break; }
+    const uint64_t cnt = g4.b - g4.a, k_next = g4.k0 + g4.ng;
+    const uint64_t blocks = (cnt / kPer4 + kThreads - 1) / kThreads;
+    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    if (j == 0) {      // cnt <= kTail4: one block
+      if (vec)
+        hipLaunchKernelGGL((dequant_w4z_kernel<true, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off, g4.k0, k_next, s_next, group);
+      else
+        hipLaunchKernelGGL((dequant_w4z_kernel<false, true>), dim3(1), dim3(kThreads), 0, st, r, g4.a, cnt, g4.p_off,
+                           g4.s_off, g4.k0, k_next, s_next, group);
+    } else {
+      if (vec)
+        hipLaunchKernelGGL((dequant_w4z_kernel<true, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off, g4.k0, k_next, s_next, group);
+      else
+        hipLaunchKernelGGL((dequant_w4z_kernel<false, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, r, g4.a,
+                           cnt, g4.p_off, g4.s_off, g4.k0, k_next, s_next, group);
+    }
+    FLS_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // bitsandbytes 4-bit (NF4 / FP4) expansion in place (flexible_llm_sharding_amd/nf4.py holds the
 // definition; the landing layout is INT4's above with blocks for groups and raw absmax entries of 1
 // (U8, double quantisation) or 4 (fp32) bytes for scales).

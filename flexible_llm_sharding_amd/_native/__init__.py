@@ -151,6 +151,12 @@ def _load_kernels(path: str = _KERNELS):
     _bind(lib, "fls_dequant_mxfp4_launches", c_int, c_uint64)
     _bind(lib, "fls_dequant_mxfp4_tail", c_int)
     _bind(lib, "fls_dequant_mxfp4_segment", c_int, c_uint64, c_int, c_void_p)
+    _bind(lib, "fls_repack_w4", c_int, c_void_p, c_uint64, c_uint64, c_uint64, c_int, c_void_p)
+    _bind(lib, "fls_repack_w4_input", c_int, c_uint64, c_uint64, c_uint64, c_void_p)
+    _bind(lib, "fls_dequant_w4z", c_int, c_void_p, c_uint64, c_uint64, c_void_p)
+    _bind(lib, "fls_dequant_w4z_launches", c_int, c_uint64, c_uint64)
+    _bind(lib, "fls_dequant_w4z_tail", c_int)
+    _bind(lib, "fls_dequant_w4z_segment", c_int, c_uint64, c_uint64, c_int, c_void_p)
     _bind(lib, "fls_gemv_skinny", c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
           c_void_p)
     _bind(lib, "fls_lora_merge", c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p, c_int,

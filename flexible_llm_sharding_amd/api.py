@@ -26,7 +26,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import knobs, quant
+from . import gptq, knobs, quant
 from .config import MAX_TOKEN_LEN, ModelConfig
 from .embed import EmbedParams
 from .embed import layer_names as mode_layer_names
@@ -111,6 +111,8 @@ def build_source(args, cfg: ModelConfig, comm: Comm, device: torch.device, lora=
         return HostStore.synthetic(cfg, device, seed=0, pinned=device.type == "cuda", names=mine, fold_norms=fold)
     src = FileLayerSource(cfg, args.model_path, names=mine, direct=getattr(args, "o_direct", False))
     tensors = src.tensors()                # (every layer's plan is made now: a bad file is refused here)
+    if tensors["gptq"] or tensors["awq"]:
+        gptq.check_quantization_config(args.model_path)     # (bits, gptq_v2, AWQ's GEMV, desc_act)
     for f in quant.ALL_FORMATS:
         if tensors[f.name] and getattr(args, "verbose", False):
             print(f.verbose.format(n=tensors[f.name], ignored=len(src.ignored_scales())), file=sys.stderr)

@@ -435,6 +435,10 @@ def merge_state_dict(sd: Dict[str, torch.Tensor], mods: Dict[str, Target], merge
     out = {}
     for k, v in sd.items():
         t = mods.get(k[:-len(".weight")]) if k.endswith(".weight") else None
+        if k.endswith(".qweight") and k[:-len(".qweight")] in mods:
+            t = mods[k[:-len(".qweight")]]
+            raise TypeError(f"{k}: {v.dtype} {tuple(v.shape)} cannot take the adapter (an fp16 / bf16 / fp32 "
+                            f"[{t.rows}, {t.cols}] weight can: merge a quantised checkpoint's fp16 twin)")
         if t is None:
             out[k] = v
             continue

@@ -312,7 +312,7 @@ def pack_layer(cfg: ModelConfig, layer_name: str, sd: Dict[str, torch.Tensor],
         key = source_key(cfg, layer_name, pl.hf_name, sd)
         fmt = quant.source(pl.hf_name, sd)[0]
         # a quantised weight: the image holds w16 (the format's own definition)
-        if fmt in quant.LANDS_SEGMENTED:
+        if fmt in quant.LANDS_IN_PIECES:
             t = quant.FORMAT_BY_NAME[fmt].module.dequantize_entry(sd, pl.hf_name, pl.shape, f"{layer_name}: ")
         else:
             t = sd[key]

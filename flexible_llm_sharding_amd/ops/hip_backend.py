@@ -771,6 +771,22 @@ class HipOps:
             raise ValueError(f"the {numel} weights of an MXFP4 tensor are no whole blocks of 32")
         _chk(self.k.fls_dequant_mxfp4(region.data_ptr(), numel, _stream()), "fls_dequant_mxfp4")
 
+    def dequant_gptq(self, region: torch.Tensor, out: int, inn: int, group: int, layout: str) -> None:
+        """Expand the GPTQ / AWQ (``layout``) weight ``[out, inn]`` in groups of ``group`` whose qweight,
+        scales and qzeros landed at the bottom of its ``2 * out * inn``-byte ``region``
+        (gptq.input_layout) to fp16 in place: one transposing launch into the segmented layout at the
+        top of the region (csrc/kernels/repack.hip), then the in-place chain with zero points
+        (csrc/kernels/dequant.hip), stream-ordered."""
+        from .. import gptq
+        if region.numel() * region.element_size() != 2 * out * inn or not region.is_contiguous():
+            raise ValueError("the region of a GPTQ / AWQ tensor is 2 bytes per weight")
+        if layout not in gptq.LAYOUT_CODES:
+            raise ValueError(f"layout {layout!r}: gptq or awq")
+        gptq.input_layout(out, inn, group)          # (bad shapes, or an input that would reach the output)
+        _chk(self.k.fls_repack_w4(region.data_ptr(), out, inn, group, gptq.LAYOUT_CODES[layout], _stream()),
+             "fls_repack_w4")
+        _chk(self.k.fls_dequant_w4z(region.data_ptr(), out * inn, group, _stream()), "fls_dequant_w4z")
+
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         views = layout.views(buf, torch.float16)
         for i, (name, v) in enumerate(views.items()):

@@ -400,6 +400,17 @@ class TorchOps:
         w = mxfp4.dequantize(packed.view(rows, mxfp4.BLOCK // 2), scales.view(rows, 1), (rows, mxfp4.BLOCK))
         b.view(torch.float16).copy_(w.reshape(-1))
 
+    def dequant_gptq(self, region: torch.Tensor, out: int, inn: int, group: int, layout: str) -> None:
+        """The GPTQ / AWQ (``layout``) weight ``[out, inn]`` whose qweight, scales and qzeros landed at
+        the bottom of its ``2 * out * inn``-byte ``region`` (gptq.input_layout) -> fp16 in place, by the
+        host definition (gptq.dequantize)."""
+        from .. import gptq
+        b = region.view(torch.uint8)
+        if b.numel() != 2 * out * inn:
+            raise ValueError("the region of a GPTQ / AWQ tensor is 2 bytes per weight")
+        qweight, scales, qzeros = gptq.unland(b.to("cpu"), out, inn, group, layout)
+        b.view(torch.float16).copy_(gptq.dequantize(qweight, qzeros, scales, layout).reshape(-1))
+
     # ------------------------------------------------------- synthetic init
     def fill_layer_random(self, buf: torch.Tensor, layout, seed: int, std: float = 0.02) -> None:
         """Random-init one packed layer in place (norm weights ~ 1, embeddings ~ N(0,1))."""

@@ -2,7 +2,8 @@
 twin writer, the ``--quantize`` dispatch and the checkpoint-name lookups of the loader.
 
 The formats themselves (value definition, converter, checks) are :mod:`.fp8`, :mod:`.int4`,
-:mod:`.nf4` and :mod:`.mxfp4`; the device kernels are ``csrc/kernels/dequant.hip``.
+:mod:`.nf4`, :mod:`.mxfp4` and :mod:`.gptq` (GPTQ and AWQ); the device kernels are
+``csrc/kernels/dequant.hip`` and ``csrc/kernels/repack.hip``.
 
 Landing layout of a 4-bit tensor (:func:`segments`).  A tensor of ``N`` weights owns its ``2N``-byte
 region of the layer image and nothing else.  The kernel expands elements ``[a, b)`` per stream-ordered
@@ -131,7 +132,7 @@ def write_twin(src_dir: str, dst_dir: str, dequantize_state_dict) -> None:
 
 
 # --------------------------------------------------------------------------- the format table
-from . import fp8, int4, mxfp4, nf4   # noqa: E402  (the 4-bit modules import the landing layout above)
+from . import fp8, gptq, int4, mxfp4, nf4   # noqa: E402  (the 4-bit modules import the landing layout above)
 
 
 class Format(NamedTuple):
@@ -155,15 +156,21 @@ SEGMENTED = ("int4", "nf4")           # the 4-bit formats: they land segment by 
 # since.  The tables below are the ones the loader, the converter and the metrics go through.
 ALL_FORMATS = FORMATS + (
     Format("mxfp4", "MXFP4", mxfp4, "MXFP4 checkpoint: {n} e2m1 tensors with e8m0 block scales are expanded to fp16 in HBM"),
+    Format("gptq", "GPTQ", gptq, "GPTQ checkpoint: {n} 4-bit tensors are repacked and expanded to fp16 in HBM"),
+    Format("awq", "AWQ", gptq, "AWQ checkpoint: {n} 4-bit GEMM-layout tensors are repacked and expanded to fp16 in HBM"),
 )
 FORMAT_BY_NAME = {f.name: f for f in ALL_FORMATS}
 LANDS_SEGMENTED = SEGMENTED + ("mxfp4",)
+# GPTQ and AWQ: the file tensors land contiguous at the bottom of the region, one launch repacks them
+# into the segmented layout at its top, then the chain expands them (gptq.py)
+LANDS_REPACKED = ("gptq", "awq")
+LANDS_IN_PIECES = LANDS_SEGMENTED + LANDS_REPACKED      # every format whose tensors land as several pieces
 
 
 def quantize_format(quantize: str) -> Format:
     """The format ``--quantize`` names; ValueError otherwise."""
     if quantize not in FORMAT_BY_NAME:
-        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4, or mxfp4")
+        raise ValueError(f"--quantize {quantize!r}: fp8, int4 or nf4, or mxfp4, gptq or awq")
     return FORMAT_BY_NAME[quantize]
 
 
@@ -172,7 +179,8 @@ def quantize_state_dict(sd: Dict[str, torch.Tensor], quantize: str, fp8_scale: s
                         nf4_double_quant: bool = True) -> Dict[str, torch.Tensor]:
     """``--quantize`` of one file's tensors: the named format's own ``quantize_state_dict`` with its
     own options."""
-    args = {"fp8": (fp8_scale,), "int4": (int4_group, int4_scale_dtype), "nf4": (nf4_block, nf4_double_quant)}
+    args = {"fp8": (fp8_scale,), "int4": (int4_group, int4_scale_dtype), "nf4": (nf4_block, nf4_double_quant),
+            "gptq": ("gptq", int4_group), "awq": ("awq", int4_group)}
     return quantize_format(quantize).module.quantize_state_dict(sd, *args.get(quantize, ()))
 
 
@@ -180,21 +188,29 @@ def quantize_state_dict(sd: Dict[str, torch.Tensor], quantize: str, fp8_scale: s
 def is_companion(name: str, want) -> bool:
     """``name`` belongs to a weight among ``want`` in some format: an FP8 scale, the words, scales or
     shape of an INT4 weight, the absmax, code books or quant state of a bitsandbytes 4-bit weight, the
-    block scales of an MXFP4 weight."""
+    block scales of an MXFP4 weight, the words, zero points, scales or group index of a GPTQ / AWQ
+    weight."""
     return ((fp8.is_scale_name(name) and fp8.weight_of_scale(name) in want)
-            or any(m.is_companion_name(name) and m.weight_of_companion(name) in want for m in (int4, nf4, mxfp4)))
+            or any(m.is_companion_name(name) and m.weight_of_companion(name) in want
+                   for m in (int4, nf4, mxfp4, gptq)))
 
 
 def source(weight_name: str, infos, where: str = "") -> Tuple[Optional[str], Optional[str]]:
     """``(format, key)`` of what feeds weight ``weight_name`` from the tensors ``infos`` (name ->
     object with a ``dtype``): the format is None for a tensor that is not quantised, the key is
-    ``X.weight_packed`` for an INT4 weight, the weight's own name otherwise, None if it is absent."""
-    pk = int4.packed_name(weight_name)
+    ``X.weight_packed`` for an INT4 weight, ``X.qweight`` for a GPTQ / AWQ weight, the weight's own
+    name otherwise, None if it is absent."""
+    pk, qk = int4.packed_name(weight_name), gptq.qweight_name(weight_name)
     if weight_name not in infos:
-        return ("int4", pk) if pk in infos else (None, None)
+        if pk in infos:
+            return "int4", pk
+        return (gptq.source_format(weight_name, infos), qk) if qk in infos else (None, None)
     if pk in infos:
         raise TypeError(f"{where}{weight_name} is stored twice, as itself and as INT4 words ({pk}); a layer file "
                         "holds one of the two")
+    if qk in infos:
+        raise TypeError(f"{where}{weight_name} is stored twice, as itself and as GPTQ / AWQ words ({qk}); a layer "
+                        "file holds one of the two")
     if nf4.is_nf4_source(weight_name, infos):
         return "nf4", weight_name
     if mxfp4.is_mxfp4_source(weight_name, infos):

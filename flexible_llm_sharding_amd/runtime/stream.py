@@ -27,6 +27,8 @@ Here the same small-RAM envelope costs no CPU work per pass:
   segment by segment into the top of the region (the landing layout of :mod:`..quant`); the scales
   travel with the weights, NF4's small tables (code books, nested absmax) are read at plan time.
   MXFP4 (:mod:`..mxfp4`) lands the same way, with blocks of 32 and one-byte scales and no tables.
+  GPTQ and AWQ (:mod:`..gptq`) are stored input-major: their three file tensors land contiguous at
+  the bottom of the region and a transposing kernel repacks them into that layout at its top.
   What is read at plan time is resident on the device in one arena per source
   (:meth:`FileLayerSource.prepare_device`).
 
@@ -47,7 +49,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from .. import _native, fp8, int4, knobs, mxfp4, nf4, quant
+from .. import _native, fp8, gptq, int4, knobs, mxfp4, nf4, quant
 from ..config import ModelConfig
 from ..models.layout import check_layer_tensors, layer_kind, layer_layout, placements, source_key
 from ..ops import get_ops
@@ -86,7 +88,12 @@ class TensorRun:
 
     ``"mxfp4"`` (:mod:`..mxfp4`): ``numel / 2`` packed bytes at ``file_off`` plus ``numel / 32`` e8m0
     scale bytes (``group`` 32, ``scale_dtype`` U8) at ``scale_off``, landing as ``mxfp4.region_layout``
-    lays them out.  No tables."""
+    lays them out.  No tables.
+
+    ``"gptq"`` / ``"awq"`` (:mod:`..gptq`): ``qweight`` (``numel / 2`` bytes) at ``file_off``, the fp16
+    ``scales`` at ``scale_off`` and ``qzeros`` at ``zero_off`` land as they are at the bottom of the
+    region (``gptq.input_layout``); ``cols`` is the row length ``in``, ``group`` the group size.
+    :meth:`expand` repacks them to the top of the region, then expands.  No tables."""
     hf_name: str
     file_off: int
     img_off: int
@@ -101,6 +108,7 @@ class TensorRun:
     scale_off: int = 0
     scale_dtype: Optional[torch.dtype] = None
     quant: Optional[nf4.QuantState] = field(default=None, compare=False, repr=False)
+    zero_off: int = 0
 
     @property
     def src_es(self) -> int:
@@ -123,9 +131,15 @@ class TensorRun:
         return self.fmt == "mxfp4"
 
     @property
+    def lands_repacked(self) -> bool:
+        """A GPTQ / AWQ tensor: its three file tensors land contiguous at the bottom of the region."""
+        return self.fmt in quant.LANDS_REPACKED
+
+    @property
     def lands_segmented(self) -> bool:
-        """A 4-bit tensor (INT4, NF4 or MXFP4): it lands segment by segment."""
-        return self.fmt in quant.LANDS_SEGMENTED
+        """A 4-bit tensor: it lands as several pieces inside its region (:meth:`landing_pieces`),
+        segment by segment (INT4, NF4, MXFP4) or tensor by tensor (GPTQ, AWQ)."""
+        return self.fmt in quant.LANDS_IN_PIECES
 
     @property
     def scale_es(self) -> int:
@@ -134,6 +148,8 @@ class TensorRun:
     @property
     def file_nbytes(self) -> int:
         """Tensor bytes of the file that a pass reads and copies for this tensor."""
+        if self.lands_repacked:
+            return sum(nb for _, nb, _ in self.landing_pieces())
         if self.lands_segmented:
             return self.numel // 2 + self.numel // self.group * self.scale_es
         return self.numel * self.src_es
@@ -145,7 +161,11 @@ class TensorRun:
 
     def landing_pieces(self) -> List[Tuple[int, int, int]]:
         """(file_off, bytes, region offset) of a 4-bit tensor's landing pieces: per segment its packed
-        bytes and, where it holds any, the raw scale bytes of the groups that end in it."""
+        bytes and, where it holds any, the raw scale bytes of the groups that end in it; of a GPTQ /
+        AWQ tensor its ``qweight``, ``scales`` and ``qzeros``."""
+        if self.lands_repacked:
+            lay = gptq.input_layout(self.numel // self.cols, self.cols, self.group)
+            return [(fo, nb, off) for fo, (off, nb) in zip((self.file_off, self.scale_off, self.zero_off), lay)]
         out = []
         for s in quant.FORMAT_BY_NAME[self.fmt].module.region_layout(self.numel, self.group, self.scale_es):
             if s.n_groups:
@@ -155,6 +175,8 @@ class TensorRun:
 
     def landing_span(self) -> Tuple[int, int]:
         """``(offset, bytes)`` of the part of a 4-bit tensor's region that its landed inputs occupy."""
+        if self.lands_repacked:
+            return gptq.landing_span(self.numel // self.cols, self.cols, self.group)
         return quant.FORMAT_BY_NAME[self.fmt].module.landing_span(self.numel, self.group, self.scale_es)
 
     def expand(self, ops, region: torch.Tensor, tables: Sequence[Optional[torch.Tensor]]) -> None:
@@ -167,6 +189,8 @@ class TensorRun:
             ops.dequant_int4(region, self.numel, self.group, self.scale_dtype)
         elif self.fmt == "mxfp4":
             ops.dequant_mxfp4(region, self.numel)
+        elif self.lands_repacked:
+            ops.dequant_gptq(region, self.numel // self.cols, self.cols, self.group, self.fmt)
         else:
             q = self.quant
             ops.dequant_nf4(region, self.numel, q.block, q.absmax_kind, *tables, q.nested_block, q.offset)
@@ -186,7 +210,7 @@ class LayerPlan:
         for pl in placements(cfg, layer_name):
             key = source_key(cfg, layer_name, pl.hf_name, infos)
             fmt = quant.source(pl.hf_name, infos)[0]
-            if fmt in quant.LANDS_SEGMENTED:
+            if fmt in quant.LANDS_IN_PIECES:
                 runs.append(getattr(self, f"_{fmt}_run")(path, pl, infos))
                 continue
             ti: TensorInfo = infos[key]
@@ -216,6 +240,8 @@ class LayerPlan:
     int4_tensors = property(lambda self: self.tensors["int4"])
     nf4_tensors = property(lambda self: self.tensors["nf4"])
     mxfp4_tensors = property(lambda self: self.tensors["mxfp4"])
+    gptq_tensors = property(lambda self: self.tensors["gptq"])
+    awq_tensors = property(lambda self: self.tensors["awq"])
 
     @staticmethod
     def _fp8_run(path: str, key: str, ti: TensorInfo, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
@@ -280,6 +306,28 @@ class LayerPlan:
             raise ValueError(f"{path}: {pk} / {sk} byte sizes do not match their shapes")
         return TensorRun(pl.hf_name, ti.begin, pl.offset, pl.numel, ti.dtype, "mxfp4", group=mxfp4.BLOCK,
                          scale_off=si.begin, scale_dtype=si.dtype)
+
+    @staticmethod
+    def _gptq_run(path: str, pl, infos: Dict[str, TensorInfo]) -> TensorRun:
+        """The run of the GPTQ or AWQ tensor that feeds placement ``pl``.  Only ``X.g_idx`` (4 bytes per
+        input) is read now, and never again: it must be ``k // g``.  Scales and zero points are read
+        with the weights, every pass."""
+        where = f"{path}: "
+        e = gptq.check_entry(pl.hf_name, infos, pl.shape, where)
+        out, inn = pl.shape
+        if e.g_idx is not None:
+            gi = infos[e.g_idx]
+            raw = torch.empty(gi.nbytes, dtype=torch.uint8)
+            hostmem.pread_into(path, gi.begin, gi.nbytes, raw)
+            gptq.check_g_idx(pl.hf_name, raw.view(torch.int32), e.group, where)
+        qi, si, zi = infos[e.qweight], infos[e.scales], infos[e.qzeros]
+        lay = gptq.input_layout(out, inn, e.group)
+        if (qi.nbytes, si.nbytes, zi.nbytes) != tuple(nb for _, nb in lay):
+            raise ValueError(f"{path}: {e.qweight} / {e.scales} / {e.qzeros} byte sizes do not match their shapes")
+        return TensorRun(pl.hf_name, qi.begin, pl.offset, pl.numel, qi.dtype, e.layout, cols=inn, group=e.group,
+                         scale_off=si.begin, scale_dtype=si.dtype, zero_off=zi.begin)
+
+    _awq_run = _gptq_run
 
     def pieces(self, lo: int = 0, hi: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
         """(file_off, file_bytes, dst_off, kind) covering image bytes [lo, hi); dst_off relative to lo.
@@ -568,6 +616,12 @@ class FileLayerSource(LayerSource):
 
     def mxfp4_tensors(self) -> int:
         return self.tensors()["mxfp4"]
+
+    def gptq_tensors(self) -> int:
+        return self.tensors()["gptq"]
+
+    def awq_tensors(self) -> int:
+        return self.tensors()["awq"]
 
     def file_bytes(self, names: Optional[Sequence[str]] = None) -> int:
         """Tensor bytes of the layer files (what a pass reads and copies)."""

@@ -267,7 +267,8 @@ class CompactHostStore(LayerSource):
     A 4-bit tensor (``TensorRun.lands_segmented``: INT4, NF4, MXFP4) is pinned as its landing image: the
     packed bytes and raw scales of its segments in the order and at the offsets they take in the
     tensor's region (the landing layout of :mod:`..quant`), so the whole tensor is still one H2D
-    (``TensorRun.landing_span``)."""
+    (``TensorRun.landing_span``).  A GPTQ / AWQ tensor likewise: its three file tensors at the offsets
+    they take at the bottom of the region (``gptq.input_layout``)."""
 
     norms_folded = False
     COMPACT_ALIGN = 16

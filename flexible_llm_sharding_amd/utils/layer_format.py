@@ -115,7 +115,11 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
     ``.quant_map``, ``.nested_*``, ``.quant_state.bitsandbytes__nf4``) in its layer file;
     ``quantize="nf4"`` writes that form from float weights (nf4.quantize_state_dict).  An MXFP4
     source checkpoint (U8 ``weight`` and U8 ``weight_scale``) passes through with its bytes unchanged;
-    ``quantize="mxfp4"`` writes that form from float weights (mxfp4.quantize_state_dict)."""
+    ``quantize="mxfp4"`` writes that form from float weights (mxfp4.quantize_state_dict).  A GPTQ or
+    AWQ source checkpoint (``qweight`` / ``qzeros`` / ``scales`` / ``g_idx``) passes through with its
+    bytes unchanged and keeps its ``quantization_config`` (``config.json`` is copied);
+    ``quantize="gptq"`` / ``"awq"`` writes those forms from float weights in groups of ``int4_group``
+    (gptq.quantize_state_dict)."""
     if quantize is not None:
         quant.quantize_format(quantize)         # (an unknown name is refused before anything is written)
     os.makedirs(out_dir, exist_ok=True)

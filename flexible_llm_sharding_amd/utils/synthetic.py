@@ -120,6 +120,8 @@ def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
     ``quantize="nf4"``: in the bitsandbytes 4-bit form, NF4 code book, blocks of ``nf4_block``, the
     absmax 8-bit quantised if ``nf4_double_quant`` (nf4.quantize_state_dict).  ``quantize="mxfp4"``:
     as OCP MXFP4, e2m1 bytes with one e8m0 scale per 32 weights (mxfp4.quantize_state_dict).
+    ``quantize="gptq"`` / ``"awq"``: in those 4-bit layouts with zero points, groups of ``int4_group``
+    (gptq.quantize_state_dict).
     ``unique_layers`` > 0: only the first K decoder layers get their own random weights;
     decoder layer i >= K is a hard link to layer i % K (a 138 GB 70B checkpoint in ~K x 1.7 GB of
     disk for streaming benchmarks — the reads are per file, as for a real checkpoint)."""

@@ -12,6 +12,8 @@
                  (the same weights in the bitsandbytes 4-bit form, NF4 code book: the QLoRA base)
                  --quantize mxfp4
                  (the same weights as OCP MXFP4: e2m1 elements, one e8m0 scale byte per 32)
+                 --quantize gptq|awq [--int4_group 128]
+                 (the same weights in AutoGPTQ's / AutoAWQ's 4-bit layout: qweight, qzeros, scales)
     python prepare_weights.py <model_dir> <new_file_dir> --merge_lora <adapter_dir> [--lora_scale 1.0]
                  (the fp16 checkpoint with a LoRA adapter merged in: what --lora computes in HBM)
 """
@@ -35,16 +37,18 @@ def main(argv=None):
                     help="--synthetic: checkpoint dtype")
     ap.add_argument("--unique_layers", type=int, default=0,
                     help="--synthetic: write K distinct decoder layers, hard-link the rest (disk-limited boxes)")
-    ap.add_argument("--quantize", choices=["fp8", "int4", "nf4", "mxfp4"], default=None,
+    ap.add_argument("--quantize", choices=["fp8", "int4", "nf4", "mxfp4", "gptq", "awq"], default=None,
                     help="write the decoder layers' 2-D projection weights (q/k/v/o, gate/up/down, fused and "
                          "expert weights) as FP8 e4m3 with fp32 scales, as INT4 (W4A16, symmetric) with group "
-                         "scales, as bitsandbytes 4-bit (NF4 code book, block absmax), or as MXFP4 (e2m1 with one e8m0 "
-                         "scale per 32 weights, no options); router, norms, biases, embedding and head stay as they are")
+                         "scales, as bitsandbytes 4-bit (NF4 code book, block absmax), as MXFP4 (e2m1 with one e8m0 "
+                         "scale per 32 weights, no options), or in GPTQ's or AWQ's (GEMM) 4-bit layout with zero "
+                         "points, round to nearest in groups of --int4_group; router, norms, biases, embedding and "
+                         "head stay as they are")
     ap.add_argument("--fp8_scale", choices=["channel", "tensor", "block128"], default="channel",
                     help="--quantize fp8: one scale per output channel / per tensor (weight_scale) or per "
                          "128x128 block (weight_scale_inv)")
     ap.add_argument("--int4_group", type=int, default=128,
-                    help="--quantize int4: weights per scale, a multiple of 32 that divides every row length "
+                    help="--quantize int4 | gptq | awq: weights per scale, a multiple of 32 that divides every row length "
                          "(0: one scale per output channel)")
     ap.add_argument("--int4_scale_dtype", choices=["float16", "bfloat16", "float32"], default="float16",
                     help="--quantize int4: dtype of the group scales")
