@@ -206,6 +206,17 @@ int fls_verify_rows(const void* probs, int ld, int rows, int V, const int* row_s
 // hipErrorInvalidValue for a missing array, H <= 0, ld < H, D outside 1 .. H or a list longer than x.
 int fls_pool_rows(const void* x, int ld, int n_src, int H, const int* row_idx, int n_list, const int* seg_start,
                   int n_seg, int D, int normalize, float* out, fls_stream_t s);
+// linear classifier / reward head on fp16 rows (csrc/kernels/classify.hip; flexible_llm_sharding_amd/classify.py
+// holds the definition).  Row r of the call is row row_index[r] of x (int32, a row of x; a negative index
+// reads row 0), or row r with row_index null; rows of x are x_stride >= H elements apart.  w16: [L, H] fp16,
+// contiguous, 1 <= L <= 64; bias: L fp32, or null.  out[r, l] fp32 (contiguous [rows, L]) =
+// act(sum_k x[row(r), k] * w16[l, k] + bias[l]) accumulated in fp32; activation 0 none, 1 softmax over the
+// row's L values (max-subtracted), 2 sigmoid.  A row's bits depend on that row, w16, bias and H only.
+// 16-byte loads when H % 32 == 0, x_stride % 8 == 0 and x, w16 are 16-byte aligned, 2-byte loads (the
+// same arithmetic) otherwise.  rows == 0 returns 0 without a launch; hipErrorInvalidValue for a missing
+// x / w16 / out, rows < 0, H <= 0, x_stride < H, L outside 1 .. 64 or an unknown activation.  One launch on s.
+int fls_classify_rows(const void* x, long long x_stride, const int* row_index, int rows, int H, const void* w16, int L,
+                      const float* bias, int activation, float* out, fls_stream_t s);
 // dst = fp16(src): src_dtype 1 = bf16 (in place allowed), 2 = fp32 (no overlap)
 int fls_cast_f16(void* dst, const void* src, int src_dtype, uint64_t n, fls_stream_t s);
 // weight-only FP8 (OCP e4m3fn) expansion in place (csrc/kernels/dequant.hip; flexible_llm_sharding_amd/fp8.py

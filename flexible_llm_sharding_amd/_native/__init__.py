@@ -65,7 +65,7 @@ class Piece(ctypes.Structure):
                 ("kind", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
-KERNELS_ABI = 42  # bumped whenever a C signature in csrc/include/fls.h (or an accepted argument) changes
+KERNELS_ABI = 43  # bumped whenever a C signature in csrc/include/fls.h (or an accepted argument) changes
 
 
 def _load_kernels(path: str = _KERNELS):
@@ -134,6 +134,8 @@ def _load_kernels(path: str = _KERNELS):
           c_void_p, c_void_p, c_void_p)
     _bind(lib, "fls_pool_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
           c_void_p, c_void_p)
+    _bind(lib, "fls_classify_rows", c_int, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_void_p, c_int,
+          c_void_p, c_int, c_void_p, c_void_p)
     _bind(lib, "fls_cast_f16", c_int, c_void_p, c_void_p, c_int, c_uint64, c_void_p)
     _bind(lib, "fls_dequant_fp8", c_int, c_void_p, c_uint64, c_void_p, c_int, c_uint64, c_void_p)
     _bind(lib, "fls_dequant_fp8_launches", c_int, c_uint64)

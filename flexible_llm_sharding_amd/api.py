@@ -28,15 +28,16 @@ import torch
 
 from . import gptq, knobs, quant
 from .config import MAX_TOKEN_LEN, ModelConfig
+from .classify import ClassifyParams
+from .classify import pass_layer_names as mode_layer_names
 from .embed import EmbedParams
-from .embed import layer_names as mode_layer_names
 from .engine import ShardedRunner
 from .parallel.comm import Comm
 from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
 from .sampling import SamplingParams, draws as sample_draws, sample_tokens
-from .utils.cli import check_embed, check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
+from .utils.cli import check_classify, check_embed, check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
 from .utils.tokenizer import load_tokenizer
 
 
@@ -235,13 +236,17 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     check_top_k(args, comm.world)
     check_lookup(args, comm.world)
     check_embed(args, cfg.hidden_size)
+    check_classify(args)
     mode = getattr(args, "score_mode", "next_token")
-    if mode in ("loglik", "embed") and comm.world > 1 and not args.data_parallel:
+    if mode in ("loglik", "embed", "classify") and comm.world > 1 and not args.data_parallel:
         raise ValueError(f"--score_mode {mode} does not combine with model parallel: pass --data_parallel")
     embed_kw = {}
     if mode == "embed":
         ep = EmbedParams.from_args(args)
         embed_kw = dict(embed_pooling=ep.pooling, embed_dim=ep.dim, embed_normalize=ep.normalize)
+    if mode == "classify":
+        cp = ClassifyParams.from_args(args)
+        embed_kw = dict(classify_rows=cp.rows, classify_activation=cp.activation)
     lora = load_lora(args, cfg)
     pkv = resolve_prefix_kv_cache(args)
     skv = resolve_suffix_kv_cache(args, comm.world) and pkv
@@ -348,8 +353,8 @@ def run_all(args, runner: ShardedRunner, comm: Comm, prompts: Sequence) -> List[
         return sum((o for o, _ in allv), [])
     if comm.world == 1:
         return outs
-    if getattr(runner, "embed", None) is not None:
-        # float32 [n_s, D] arrays: gathered as objects (gather_scores packs fp16 and would round them)
+    if getattr(runner, "embed", None) is not None or getattr(runner, "classify", None) is not None:
+        # float32 [n_s, D] / [*, L] arrays: gathered as objects (gather_scores packs fp16 and would round them)
         allv = comm.gather_object(outs, dst=0)
         return sum(allv, []) if comm.rank == 0 else []
     if getattr(runner, "score_top_k", 0):
@@ -655,6 +660,15 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
                   "normalized": ep.normalize}
         updated = copy.deepcopy(list(original))
         step_times.append(time.perf_counter() - t1)
+    elif getattr(args, "score_mode", "next_token") == "classify":
+        # one pass, no token to append: the prompts are written back as they came; the output file
+        # holds the head's float32 values ([n_s, L] per prompt, or per suffix [len_s, L]) and how they
+        # were taken
+        cp = runner.classify
+        scores = {"logits": run_all(args, runner, comm, list(original)), "rows": cp.rows,
+                  "activation": cp.activation, "num_labels": cp.num_labels}
+        updated = copy.deepcopy(list(original))
+        step_times.append(time.perf_counter() - t1)
     else:
         rec: dict = {}
         scores, updated = generation_loop(args, runner, comm, tok, original, step_times, token_record=rec,
@@ -680,6 +694,9 @@ def run_rank(args, comm: Comm) -> Optional[dict]:
     if getattr(runner, "embed", None) is not None:
         metrics.update({"embed_pooling": runner.embed.pooling, "embed_dim": runner.embed.dim,
                         "embed_normalize": runner.embed.normalize})
+    if getattr(runner, "classify", None) is not None:
+        metrics.update({"classify_rows": runner.classify.rows, "classify_activation": runner.classify.activation,
+                        "num_labels": runner.classify.num_labels})
     if getattr(args, "lookup_decoding", 0):
         metrics["lookup_decoding"] = int(args.lookup_decoding)
         metrics["lookup_ngram"] = int(getattr(args, "lookup_ngram", 3))

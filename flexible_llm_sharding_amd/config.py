@@ -55,6 +55,9 @@ class ModelConfig:
     residual_multiplier: float = 1.0
     attention_multiplier: Optional[float] = None
     logits_scaling: float = 1.0
+    # *ForSequenceClassification / *ForTokenClassification configs: rows of the head score.weight
+    # (num_labels, else len(id2label)); None for a plain LM config (classify.py)
+    num_labels: Optional[int] = None
     bos_token_id: int = 1
     eos_token_id: int = 2
     torch_dtype: str = "float16"
@@ -238,6 +241,8 @@ class ModelConfig:
         # use_sliding_window
         if not d.get("use_sliding_window", mt in ("mistral", "phi3", "mixtral")):
             kw.pop("sliding_window", None)
+        if kw.get("num_labels") is None and isinstance(d.get("id2label"), dict) and d["id2label"]:
+            kw["num_labels"] = len(d["id2label"])
         if isinstance(kw.get("eos_token_id"), list):
             kw["eos_token_id"] = kw["eos_token_id"][0]
         cfg = cls(**kw)
@@ -252,12 +257,16 @@ class ModelConfig:
     def to_dict(self) -> dict:
         d = asdict(self)
         d["head_dim"] = self.head_dim
+        if d.get("num_labels") is None:
+            d.pop("num_labels", None)
         return d
 
     def save(self, model_path: str) -> None:
         os.makedirs(model_path, exist_ok=True)
         d = asdict(self)
         d["head_dim"] = self.head_dim           # HF key (also read back by from_dict)
+        if d.get("num_labels") is None:
+            d.pop("num_labels", None)               # (a plain LM config names none)
         if self.model_type in ("qwen3_moe", "qwen2_moe"):
             d["num_experts"] = self.num_local_experts          # the HF key of these families
         with open(os.path.join(model_path, "config.json"), "w") as f:

@@ -35,8 +35,9 @@ import torch
 
 from . import knobs
 from .config import MAX_TOKEN_LEN, ModelConfig
+from .classify import ClassifyParams, head_for
+from .classify import pass_layer_names as mode_layer_names
 from .embed import EmbedParams
-from .embed import layer_names as mode_layer_names
 from .models.layout import layer_kind
 from .models.llama import ExecContext, layer_flops, rope_tables, run_layer
 from .ops import get_ops
@@ -86,11 +87,13 @@ class ShardedRunner:
                  max_vram_gb: Optional[float] = None, hbm_cache_gb: float = 0.0, rx_window: int = 2,
                  exact_reuse: bool = True, sliding_window_mode: str = "error", score_mode: str = "next_token",
                  sampling=None, score_top_k: int = 0, embed_pooling: Optional[str] = None,
-                 embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None, lora=None):
+                 embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None, lora=None,
+                 classify_rows: Optional[str] = None, classify_activation: Optional[str] = None,
+                 classify_head=None):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
-        if score_mode not in ("next_token", "loglik", "embed"):
-            raise ValueError(f"score_mode={score_mode!r}: 'next_token', 'loglik' or 'embed'")
+        if score_mode not in ("next_token", "loglik", "embed", "classify"):
+            raise ValueError(f"score_mode={score_mode!r}: 'next_token', 'loglik' or 'embed' (or 'classify')")
         self.score_mode = score_mode
         self.loglik = score_mode == "loglik"
         # pooled final hidden states per suffix (embed.py): the pass ends at model.norm, whose rows are
@@ -100,6 +103,13 @@ class ShardedRunner:
                                 ("--embed_normalize", embed_normalize)) if v is not None]
         if given and score_mode != "embed":
             raise ValueError(f"{given[0]} needs --score_mode embed")
+        # a linear head on the final-norm rows (classify.py): an embed pass whose norm ends in
+        # ops.classify_rows instead of the pooling
+        self.classify: Optional[ClassifyParams] = None
+        given = [f for f, v in (("--classify_rows", classify_rows), ("--classify_activation", classify_activation),
+                                ("classify_head", classify_head)) if v is not None]
+        if given and score_mode != "classify":
+            raise ValueError(f"{given[0]} needs --score_mode classify")
         # loglik and embed are one full pass each (every suffix token scored / pooled): the paths that
         # replay, reuse or hand over parts of a pass are not wired for them, and they draw and rank
         # no token
@@ -110,6 +120,8 @@ class ShardedRunner:
         mp = [(world > 1 and not data_parallel, "model parallel (several GPUs without --data_parallel)")]
         for mode, on, msg in (
                 [("embed", on, f"--score_mode embed does not combine with {flag}") for on, flag in partial + tokens + mp]
+                + [("classify", on, f"--score_mode classify does not combine with {flag}")
+                   for on, flag in partial + tokens + mp]
                 + [("loglik", on, f"--score_mode loglik does not combine with {flag}") for on, flag in partial + mp]
                 + [("loglik", on, f"{flag} does not combine with --score_mode loglik") for on, flag in tokens]):
             if on and score_mode == mode:
@@ -120,7 +132,10 @@ class ShardedRunner:
                                      ).resolved(cfg.hidden_size)
         # every suffix row leaves the last decoder layer (loglik: each is scored; mean pooling: each
         # is pooled), so that layer runs unpruned and the final norm gathers the rows
-        self._all_suffix_rows = self.loglik or (self.embed is not None and self.embed.pooling == "mean")
+        if score_mode == "classify":
+            self.classify = ClassifyParams(classify_rows or "last", classify_activation or "none")   # (+ the head below)
+        self._all_suffix_rows = (self.loglik or (self.embed is not None and self.embed.pooling == "mean")
+                                 or (self.classify is not None and self.classify.rows == "all"))
         # (mean pooling's other variant, kept for measurements — set_mean_variant: the last layer
         # pruned to the suffix rows through pack_prompts(score_rows=...); profiles/embed has both)
         self._mean_pruned = False
@@ -201,6 +216,16 @@ class ShardedRunner:
             # an FP8 checkpoint's scales go to the device now (one allocation), before any memory is
             # measured for a VRAM plan
             source.prepare_device(self.dev)
+        # the classifier head (classify.Head: at most 64 x H fp16 plus the bias) goes to a device buffer
+        # of its own now too, for the runner's lifetime
+        self.classify_head = None
+        if self.classify is not None:
+            head = classify_head if classify_head is not None else head_for(cfg, source)
+            if tuple(head.w16.shape[1:]) != (cfg.hidden_size,) or head.w16.dtype != torch.float16:
+                raise ValueError(f"classify_head: score.weight must be fp16 [L, {cfg.hidden_size}], got "
+                                 f"{head.w16.dtype} {tuple(head.w16.shape)}")
+            self.classify = self.classify.resolved(head.num_labels)
+            self.classify_head = head.to(self.dev)
         # a LoRA adapter (lora.LoraAdapter), merged into the weights as they land: its staging buffer
         # (the largest layer's A + Bs) is allocated now too, so a VRAM plan sees it as context
         self.lora = lora
@@ -265,6 +290,7 @@ class ShardedRunner:
         self.ctx.prune_last = bool(prune_last_layer and decs and not self._all_suffix_rows)
         self.ctx.loglik = self.loglik
         self.ctx.embed = self.embed
+        self.ctx.classify = (self.classify, self.classify_head) if self.classify is not None else None
         self.ctx.last_decoder = decs[-1] if decs else ""
         my = [s for s in self.plan.my_shards if len(s)]
         self.my_shards = my
@@ -332,7 +358,7 @@ class ShardedRunner:
         self._spec: Optional[dict] = None     # an enqueued speculative generation step
         # everything between the last layer's result and the caller's arrays (runtime/outputs.py)
         self.out = Outputs(score_mode, self.score_top_k, sampling, self.embed, self.ops, self.dev,
-                           self._get_store, self.d2h_stream)
+                           self._get_store, self.d2h_stream, classify=self.classify)
         self._publish(CallResults())
         if self.cuda and not self.hip_graphs:
             from .models.llama import Workspace
@@ -376,6 +402,8 @@ class ShardedRunner:
             return (batch.num_tokens, self.cfg.hidden_size)
         if kind == "norm" and self.embed is not None:
             return (len(batch.seg_start) - 1, self.embed.dim)      # fp32 pooled embeddings per suffix
+        if kind == "norm" and self.classify is not None:
+            return (int(batch.seg_start[-1]), self.classify.num_labels)    # fp32 head values per returned row
         if kind == "norm":
             return (batch.n_scored, self.cfg.hidden_size)
         if self.loglik:
@@ -389,6 +417,8 @@ class ShardedRunner:
         count, 1.0 if every token is the greedy one), per-token values in ``last_token_logprobs``.
         ``score_mode="embed"``: list of [n_s, D] float32 arrays (embed.py: each suffix's pooled
         final-norm rows).
+        ``score_mode="classify"``: list of [n_s, L] float32 arrays (classify.py: the head on each
+        suffix's last final-norm row), or with ``classify_rows="all"`` a list of n_s [len_s, L] arrays.
         ``score_top_k=K``: list of ``TOPK_DTYPE`` [n_s, 1, K] arrays (the K best (id, probability)
         pairs in rank order, topk.py), the chosen tokens' probabilities in ``last_token_probs``."""
         if self.my_shards and prompts and not self.resume_dir and not self.hip_graphs:
@@ -558,6 +588,16 @@ class ShardedRunner:
                     raise ValueError(f"score_mode='embed' with --embed_pooling mean: suffix {s} of prompt {i} "
                                      "has no token to pool")
 
+    def _check_classify(self, tps) -> None:
+        """A classify call over every suffix token needs a token in every suffix."""
+        if self.classify.rows != "all":
+            return
+        for i, tp in enumerate(tps):
+            for s, (ids, e) in enumerate(zip(tp.suffixes, tp.eos_index)):
+                if e < 0 or not ids:
+                    raise ValueError(f"score_mode='classify' with --classify_rows all: suffix {s} of prompt {i} "
+                                     "has no token to classify")
+
     def set_mean_variant(self, pruned: bool) -> None:
         """Mean pooling: run the last decoder layer unpruned (default; every row computed, the norm
         gathers the suffix rows) or pruned to the suffix rows (one single-query attention item per
@@ -574,6 +614,8 @@ class ShardedRunner:
         V = self.cfg.vocab_size
         if self.embed is not None:
             raise ValueError("drafts do not combine with score_mode='embed' (--lookup_decoding)")
+        if self.classify is not None:
+            raise ValueError("drafts do not combine with score_mode='classify' (--lookup_decoding)")
         if not self.row_exact:
             raise ValueError("drafts need the prefix K/V cache and exact_reuse (row-exact calls): a verified "
                              "row's scores must be those of the call that computes it alone")
@@ -625,6 +667,10 @@ class ShardedRunner:
             if self._mean_pruned:
                 # every suffix row is a scored row of the pruned last layer, pooled per suffix
                 score_rows, pool = [[len(s) for s in tp.suffixes] for tp in tps], "last"
+        if self.classify is not None:
+            self._check_classify(tps)
+            # the packing of embed's poolings: one row per suffix, or every suffix row in order
+            pool = "mean" if self.classify.rows == "all" else "last"
         window = self._call_window(tps)
         entry, cached = self._prefix_entry(tps)
         if self._vram_cap:
@@ -1481,6 +1527,8 @@ class ShardedRunner:
         if self.lora_staging is not None:
             self.lora_staging.release()    # (the prefetcher's close synchronised the copy stream)
             self.lora_staging = None
+        self.classify_head = None
+        self.ctx.classify = None
         if hasattr(self.src, "close"):
             self.src.close()           # the streaming source's pinned ring
         if self._store is not None:

@@ -205,6 +205,9 @@ class ExecContext:
     # arena holds); there is no head layer
     embed: Optional[object] = None
     pool_chunk: int = 0
+    # a classifier head (engine score_mode="classify"): (classify.ClassifyParams, classify.Head on the
+    # device); the final norm ends in ops.classify_rows on the returned rows, chunked like the pooling
+    classify: Optional[tuple] = None
     ss_buf: Optional[torch.Tensor] = None      # the arena-backed buffer (grown, reused)
     ss_cur: Optional[torch.Tensor] = None      # the buffer the last residual GEMM wrote
     ss_key: Optional[tuple] = None
@@ -608,7 +611,7 @@ def _shared_expert(ctx: ExecContext, W: Dict[str, torch.Tensor], h: torch.Tensor
 
 
 def run_norm(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, meta: dict, batch=None) -> torch.Tensor:
-    if ctx.embed is not None:
+    if ctx.embed is not None or ctx.classify is not None:
         return _norm_pool(ctx, W, x, meta, batch)
     if ctx.prune_last and ctx.last_decoder:
         return ctx.ops.rmsnorm(x, W["norm"], ctx.cfg.rms_norm_eps)    # rows already gathered
@@ -619,13 +622,18 @@ def _norm_pool(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, me
     """The final norm of an embed-mode pass: [n_suffixes, D] fp32 pooled embeddings (embed.py).
     The normed rows exist one chunk of whole suffixes at a time, in the workspace arena (idle in
     the norm phase); ``rmsnorm`` and ``pool_rows`` are both per-row / per-suffix, so the chunking
-    does not change a bit of the result."""
+    does not change a bit of the result.  A classify-mode pass ends the same way in
+    ``classify_rows``: [returned rows, L] fp32 head values (classify.py), per row too."""
     ops, ep, eps = ctx.ops, ctx.embed, ctx.cfg.rms_norm_eps
+    cp, head = ctx.classify if ctx.classify is not None else (None, None)
     H = x.shape[1]
     gathered = bool(ctx.prune_last and ctx.last_decoder)       # x holds the scored rows, in order
     idx, seg_dev, seg = meta["last_idx"], meta["seg_start"], batch.seg_start
     n_seg, n_rows = len(seg) - 1, int(seg[-1])
-    out = torch.empty(n_seg, ep.dim, dtype=torch.float32, device=x.device)
+    if cp is not None:
+        out = torch.empty(n_rows, cp.num_labels, dtype=torch.float32, device=x.device)
+    else:
+        out = torch.empty(n_seg, ep.dim, dtype=torch.float32, device=x.device)
     ws = ctx.ws
     cap = n_rows
     if ws is not None and ws.buf is not None:
@@ -653,6 +661,10 @@ def _norm_pool(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tensor, me
             y = ops.gather_rmsnorm(src, rows, W["norm"], eps)
         else:
             y = ops.rmsnorm(src, W["norm"], eps)
+        if cp is not None:
+            ops.classify_rows(y, head.w16, head.bias, cp.activation, out=out[a:b])
+            i0 = i1
+            continue
         ss = seg_dev[i0:i1 + 1] if a == 0 else seg_dev[i0:i1 + 1] - a
         ops.pool_rows(y, ss.contiguous(), ep.dim, ep.normalize, out=out[i0:i1])
         i0 = i1

@@ -690,6 +690,46 @@ class HipOps:
              "fls_pool_rows")
         return out
 
+    def classify_rows(self, x, w16, bias=None, activation: str = "none", row_idx=None, out=None):
+        """[rows, L] fp32: ``act(x[row] . w16[l] + bias[l])`` accumulated in fp32 (classify.py holds the
+        definition; ``fls_classify_rows``).  ``x``: fp16 [n, H] with unit column stride (any row stride
+        >= H, any 2-byte aligned base); the rows are ``x[row_idx]`` (int32 CUDA vector of rows of x) or
+        ``x`` itself; ``w16``: contiguous fp16 [L, H], 1 <= L <= 64; ``bias``: contiguous fp32 [L] or
+        None; ``activation``: none | softmax | sigmoid.  A row's bits depend on that row, ``w16``,
+        ``bias`` and H only."""
+        from ..classify import ACTIVATIONS, MAX_LABELS
+        _f16(x, "x")
+        _f16(w16, "w16")
+        if x.dim() != 2 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            raise TypeError("x must be a [rows, H] tensor with unit column stride and a row stride >= H")
+        H = x.shape[1]
+        if w16.dim() != 2 or w16.shape[1] != H or not w16.is_contiguous() or w16.device != x.device:
+            raise TypeError(f"w16 must be a contiguous fp16 [L, {H}] tensor on x's device")
+        L = w16.shape[0]
+        if not 1 <= L <= MAX_LABELS:
+            raise ValueError(f"L in 1..{MAX_LABELS} expected, got {L}")
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {ACTIVATIONS}, got {activation!r}")
+        if activation == "softmax" and L == 1:
+            raise ValueError("softmax over one label is the constant 1")
+        if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (L,) or not bias.is_contiguous()
+                                 or bias.device != x.device):
+            raise TypeError(f"bias must be a contiguous fp32 [{L}] tensor on x's device")
+        if row_idx is not None and (row_idx.dtype != torch.int32 or row_idx.dim() != 1 or not row_idx.is_contiguous()
+                                    or row_idx.device != x.device):
+            raise TypeError("row_idx must be a contiguous int32 vector on x's device")
+        rows = row_idx.numel() if row_idx is not None else x.shape[0]
+        if rows and x.shape[0] == 0:
+            raise ValueError("row_idx names rows of an empty x")
+        if out is None:
+            out = torch.empty(rows, L, dtype=torch.float32, device=x.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (rows, L) or not out.is_contiguous():
+            raise TypeError(f"out must be a contiguous fp32 [{rows}, {L}] tensor")
+        _chk(self.k.fls_classify_rows(x.data_ptr(), x.stride(0), row_idx.data_ptr() if row_idx is not None else None,
+                                      rows, H, w16.data_ptr(), L, bias.data_ptr() if bias is not None else None,
+                                      ACTIVATIONS.index(activation), out.data_ptr(), _stream()), "fls_classify_rows")
+        return out
+
     def cast_f16(self, dst: torch.Tensor, src: torch.Tensor, src_code: int) -> None:
         """dst (fp16 bytes) = fp16(src bytes of bf16 (code 1; may be in place) or fp32 (code 2))."""
         n = dst.numel() * dst.element_size() // 2

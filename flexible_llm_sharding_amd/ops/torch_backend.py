@@ -255,6 +255,27 @@ class TorchOps:
             return out
         return res
 
+    def classify_rows(self, x: torch.Tensor, w16: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      activation: str = "none", row_idx: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
+        """HipOps.classify_rows in fp32 (classify.py's definition): ``act(x[row] . w16[l] + bias[l])``."""
+        from ..classify import ACTIVATIONS
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {ACTIVATIONS}, got {activation!r}")
+        if activation == "softmax" and w16.shape[0] == 1:
+            raise ValueError("softmax over one label is the constant 1")
+        rows = x.index_select(0, row_idx.long()) if row_idx is not None else x
+        z = rows.float() @ w16.float().t()
+        if bias is not None:
+            z = z + bias.float()
+        if activation == "softmax":
+            z = torch.softmax(z, dim=1)
+        elif activation == "sigmoid":
+            z = torch.sigmoid(z)
+        if out is not None:
+            out.copy_(z)
+            return out
+        return z
+
     def row_exact(self, on: bool = True):
         """HipOps.row_exact: nothing to select here (one matmul path)."""
         import contextlib

@@ -67,6 +67,7 @@ class SlicedHostStore(HostStore):
                     names: Optional[Sequence[str]] = None) -> "SlicedHostStore":
         """Read only this rank's byte slices of every layer (``read_range_into``)."""
         st = cls(src.cfg, rank, world, src.dtype, pinned, names)
+        st.model_path = getattr(src, "model_path", None)
         for n in st.names:
             buf = hostmem.alloc_host(st.chunk_bytes(n), pinned=pinned)
             for p in st.slices(n):
@@ -84,6 +85,7 @@ class SlicedHostStore(HostStore):
         st = cls(cfg, rank, world, torch.float16, pinned, names)
         st.buffers = base.buffers
         st.norms_folded = base.norms_folded
+        st.synthetic_seed = seed
         return st
 
     lora_at_build = False           # a slice cannot be merged alone: the gathered layer is, as it lands
@@ -328,13 +330,17 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
     from ..runtime.stream import FileLayerSource
     from .planner import make_plan
     device = torch.device(device)
-    from ..embed import EmbedParams, layer_names as mode_layer_names
+    from ..classify import ClassifyParams, pass_layer_names as mode_layer_names
+    from ..embed import EmbedParams
     mode = getattr(args, "score_mode", "next_token")
-    names = mode_layer_names(cfg, mode)              # (embed: no lm_head, which need not exist)
+    names = mode_layer_names(cfg, mode)              # (embed / classify: no lm_head, which need not exist)
     embed_kw = {}
     if mode == "embed":
         ep = EmbedParams.from_args(args)
         embed_kw = dict(embed_pooling=ep.pooling, embed_dim=ep.dim, embed_normalize=ep.normalize)
+    if mode == "classify":
+        cp = ClassifyParams.from_args(args)
+        embed_kw = dict(classify_rows=cp.rows, classify_activation=cp.activation)
     if store is None and getattr(args, "synthetic", None):
         from .. import knobs
         store = SlicedHostStore.synthetic(cfg, device, comm.rank, comm.world, pinned=device.type == "cuda",

@@ -1,7 +1,7 @@
 """The output path: from "the last layer produced ``probs`` for a micro-batch" to "the caller's
 arrays exist on the host".
 
-One :class:`Outputs` per runner, built from its fixed mode (``next_token`` / ``loglik`` / ``embed``,
+One :class:`Outputs` per runner, built from its fixed mode (``next_token`` / ``loglik`` / ``embed`` / ``classify``,
 ``score_top_k``, sampling), with three entry points: :meth:`Outputs.pick` (the next token of every
 row), :meth:`Outputs.start` (the device-to-host copy of a micro-batch's result -> a
 :class:`Pending`) and :meth:`Outputs.collect` (finished copies split back into prompts, into the
@@ -61,15 +61,17 @@ class CallResults:
 
 class Outputs:
     def __init__(self, mode: str, score_top_k: int, sampling, embed: Optional[EmbedParams], ops, device,
-                 get_store: Callable, d2h_stream):
+                 get_store: Callable, d2h_stream, classify=None):
         self.mode, self.score_top_k, self.sampling, self.embed = mode, int(score_top_k), sampling, embed
+        self.classify = classify                 # classify.ClassifyParams (resolved), or None
         self.ops, self.dev, self.get_store, self.d2h_stream = ops, device, get_store, d2h_stream
         self.cuda = device.type == "cuda"
         self._table = None
         if sampling is not None:
             # the weight table, uploaded once (every weight is <= 2^30: the uint32 values as int32)
             self._table = torch.from_numpy(sampling.table().view(np.int32)).to(device)
-        self._split = {"loglik": self._split_loglik, "embed": self._split_embed}.get(mode, self._split_scores)
+        self._split = {"loglik": self._split_loglik, "embed": self._split_embed,
+                       "classify": self._split_classify}.get(mode, self._split_scores)
 
     # ------------------------------------------------------------------ pick
     def pick(self, batch: PackedBatch, probs: torch.Tensor, step: int, prompt_base: int = 0) -> torch.Tensor:
@@ -94,7 +96,7 @@ class Outputs:
         ordered before the next graph replay): its probabilities and their picked tokens (the token
         of each suffix: api.generation_loop needs no host pass over the [n_s, V] scores);
         ``score_top_k``: the K best entries and the tokens' probabilities instead; loglik / embed:
-        the fp32 [n_pairs, 2] head state / [n_sfx, D] norm state as it is; a drafted micro-batch:
+        the fp32 [n_pairs, 2] head state / [n_sfx, D] norm state as it is (classify: [rows, L]); a drafted micro-batch:
         its kept rows."""
         if batch.draft is not None:
             return self._start_drafted(batch, probs, stream)
@@ -268,3 +270,19 @@ class Outputs:
             ns = batch.n_suffix[j]
             res.outputs[pid] = emb[r:r + ns].copy()
             r += ns
+
+    def _split_classify(self, p: Pending, host, res: CallResults) -> None:
+        """The [rows, L] float32 head values of a finished micro-batch (prompt -> suffix -> token
+        order; ``batch.seg_start`` holds each suffix's range) split back into prompts: ``last`` one
+        [n_s, L] array per prompt, ``all`` a list of n_s [len_s, L] arrays."""
+        batch, (val,) = p.batch, host
+        seg = batch.seg_start
+        assert val.dtype == np.float32 and val.shape == (int(seg[-1]), self.classify.num_labels), (val.dtype, val.shape)
+        i = 0
+        for j, pid in enumerate(batch.prompt_ids):
+            ns = batch.n_suffix[j]
+            if self.classify.rows == "all":
+                res.outputs[pid] = [val[int(seg[k]):int(seg[k + 1])].copy() for k in range(i, i + ns)]
+            else:
+                res.outputs[pid] = val[int(seg[i]):int(seg[i + ns])].copy()
+            i += ns

@@ -69,6 +69,8 @@ class HostStore(LayerSource):
     # lora_at_build: the store holds whole fp16 layers, so an adapter is merged once (merge_lora)
     lora_merged = None
     lora_at_build = True
+    model_path = None           # the directory the layers were read from (from_source), if any
+    synthetic_seed = None       # the seed of generated weights (synthetic), if any
     _pinning_full = False       # hipHostMalloc refused a layer: the rest of the store is pageable
 
     def __init__(self, cfg: ModelConfig, dtype=torch.float16, pinned: bool = True,
@@ -174,6 +176,7 @@ class HostStore(LayerSource):
     def from_source(cls, src: LayerSource, pinned: bool = True, threads: int = 4,
                     names: Optional[Sequence[str]] = None) -> "HostStore":
         st = cls(src.cfg, src.dtype, pinned, names)
+        st.model_path = getattr(src, "model_path", None)     # (classify.head_for: score.safetensors lies there)
         for n in st.names:
             st.alloc(n)
         errs: List[BaseException] = []
@@ -220,6 +223,7 @@ class HostStore(LayerSource):
         from ..models.llama import fold_layer_norms
         from ..ops import get_ops
         st = cls(cfg, torch.float16, pinned, names)
+        st.synthetic_seed = seed                             # (classify.head_for: the seeded score layer)
         dev = torch.device(device)
         ops = get_ops(dev)
         maxb = max((st.nbytes(n) for n in st.names), default=0)   # an MP rank may own no layers

@@ -55,7 +55,7 @@ def build_parser() -> argparse.ArgumentParser:
                         "prompt longer than it: error (default) refuses the call; apply runs sliding-window "
                         "attention (a query sees the last sliding_window positions, its own included; calls that "
                         "fit the window run unchanged)")
-    p.add_argument("--score_mode", choices=["next_token", "loglik", "embed"], default="next_token",
+    p.add_argument("--score_mode", choices=["next_token", "loglik", "embed", "classify"], default="next_token",
                    help="next_token (default): the next-token distribution after each suffix ([n_s, 1, V] fp16 per "
                         "prompt).  loglik: log p(suffix | prefix), summed over the suffix's tokens in one pass "
                         "([n_s, 3] float32 per prompt: the sum, the token count, 1 if every token is the greedy "
@@ -64,7 +64,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "parallel.  embed: each suffix's pooled final-norm hidden state ([n_s, D] float32 per "
                         "prompt; --embed_pooling, --embed_dim, --embed_normalize); the pass ends at model.norm, so "
                         "a model directory without lm_head.safetensors runs.  Not with what loglik refuses, nor "
-                        "with --do_sample, --score_top_k or --lookup_decoding")
+                        "with --do_sample, --score_top_k or --lookup_decoding.  classify: the checkpoint's linear "
+                        "head score.weight [L, H] (reward models, *ForSequenceClassification / "
+                        "*ForTokenClassification) applied to the final-norm rows on the device (float32 [n_s, L] "
+                        "per prompt, or with --classify_rows all a [len_s, L] array per suffix; "
+                        "--classify_activation); needs score.safetensors, no lm_head.safetensors; refuses what "
+                        "embed refuses")
+    p.add_argument("--classify_rows", choices=["last", "all"], default=None,
+                   help="with --score_mode classify: last (default): the row of each suffix's last token (sequence "
+                        "classification, reward models); all: every suffix token in order (token classification, "
+                        "process reward models); prefix rows are never returned")
+    p.add_argument("--classify_activation", choices=["none", "softmax", "sigmoid"], default=None,
+                   help="with --score_mode classify: applied to each row's L values in fp32 (default none: the "
+                        "logits); softmax is refused for a head with one label")
     p.add_argument("--embed_pooling", choices=["last", "mean"], default=None,
                    help="with --score_mode embed: last (default): the final-norm row of the suffix's last token "
                         "(the row the LM head scores); mean: the fp32 mean of the final-norm rows of the suffix's "
@@ -226,6 +238,32 @@ def check_embed(args, hidden_size: int = 0) -> None:
             raise ValueError(f"--score_mode embed does not combine with {flag}")
 
 
+def check_classify(args) -> None:
+    """``--score_mode classify`` and the ``--classify_*`` flags: no ``--classify_*`` flag without the
+    mode, no ``--embed_*`` flag with it (``check_embed``), and none of the modes embed refuses; a
+    ``ValueError`` names the flag."""
+    from ..classify import check_classify_values
+    rows, act = getattr(args, "classify_rows", None), getattr(args, "classify_activation", None)
+    if getattr(args, "score_mode", "next_token") != "classify":
+        for v, flag in ((rows, "--classify_rows"), (act, "--classify_activation")):
+            if v is not None:
+                raise ValueError(f"{flag} needs --score_mode classify")
+        return
+    check_classify_values(rows or "last", act or "none")
+    sampled = (getattr(args, "do_sample", False) or getattr(args, "temperature", 1.0) != 1.0
+               or getattr(args, "top_k", 0) != 0 or getattr(args, "top_p", 1.0) != 1.0)
+    for bad, flag in ((getattr(args, "num_gen_token", 1) != 1, "--num_gen_token other than 1"),
+                      (sampled, "--do_sample (and --temperature / --top_k / --top_p)"),
+                      (getattr(args, "score_top_k", 0), "--score_top_k"),
+                      (getattr(args, "lookup_decoding", 0), "--lookup_decoding"),
+                      (getattr(args, "hip_graphs", False), "--hip_graphs"),
+                      (getattr(args, "prefix_kv_cache", False) is True, "--prefix_kv_cache true"),
+                      (getattr(args, "suffix_kv_cache", False) is True, "--suffix_kv_cache true"),
+                      (getattr(args, "resume_dir", None), "--resume_dir")):
+        if bad:
+            raise ValueError(f"--score_mode classify does not combine with {flag}")
+
+
 def check_lora(args) -> None:
     """``--lora`` / ``--lora_scale``: one adapter directory, no scale without an adapter, and no
     adapter on ``--synthetic`` weights; a ``ValueError`` names the flag."""
@@ -303,6 +341,7 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     check_score_mode(args)
     check_embed(args)
+    check_classify(args)
     check_sampling(args)
     check_top_k(args)
     check_lookup(args)

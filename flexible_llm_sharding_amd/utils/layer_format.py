@@ -30,14 +30,20 @@ from .safetensors_io import load_file, save_file
 def canonical_param(name: str) -> str:
     """The tensor's name in a causal-LM checkpoint.  ``AutoModel.save_pretrained`` (the published
     embedding checkpoints) writes the bare model's names — ``embed_tokens.weight``, ``layers.N.*``,
-    ``norm.weight`` — which get the ``model.`` prefix here, so their layer files are the usual ones."""
+    ``norm.weight`` — which get the ``model.`` prefix here, so their layer files are the usual ones.
+    A classifier head is ``score.*`` in either naming (``score.safetensors``, classify.py)."""
+    if name.startswith("model.score."):
+        return name[len("model."):]    # (a head saved under the body's prefix)
     return "model." + name if name.startswith(("embed_tokens.", "layers.", "norm.")) else name
 
 
 def layer_of_param(name: str) -> str:
     """prepare_weights.py:21 — first three dotted components after stripping '.weight' (of the
     canonical name: a prefix-less ``layers.0.self_attn.q_proj.weight`` belongs to ``model.layers.0``)."""
-    return ".".join(canonical_param(name).replace(".weight", "").split(".")[:3])
+    name = canonical_param(name)
+    if name.startswith("score."):
+        return "score"                 # the classifier head (classify.py): score.weight and score.bias together
+    return ".".join(name.replace(".weight", "").split(".")[:3])
 
 
 def normalize_expert_names(model_type: str, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -168,7 +174,7 @@ def split_into_layers(src_dir: str, out_dir: str, verbose: bool = True, quantize
             sd[canonical_param(p)] = cache[wmap[p]][p]
         assert len(sd) == len(layer_params[l]), f"Should have {len(layer_params[l])} keys for {l}"
         out_sd = normalize_expert_names(model_type, sd)
-        if quantize:
+        if quantize and l != "score":              # (the head stays as it is: a quantised one is refused)
             out_sd = quant.quantize_state_dict(out_sd, quantize, fp8_scale, int4_group, int4_scale_dtype, nf4_block,
                                                nf4_double_quant)
         save_file(out_sd, layer_file(out_dir, l))

@@ -113,8 +113,11 @@ def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
                                std: float = 0.02, dtype=torch.float16, unique_layers: int = 0,
                                device="cpu", progress=None, quantize: str = None, fp8_scale: str = "channel",
                                int4_group: int = 128, int4_scale_dtype=torch.float16, nf4_block: int = 64,
-                               nf4_double_quant: bool = True) -> None:
-    """``quantize="fp8"``: the decoder layers' projection weights are written as FP8 (e4m3fn) with
+                               nf4_double_quant: bool = True, score_labels: int = 0,
+                               score_bias: bool = True) -> None:
+    """``score_labels`` > 0: also a seeded classifier head ``score.safetensors`` of that many labels
+    (classify.synthetic_head; ``score_bias``: with a bias), and ``num_labels`` in the config.
+    ``quantize="fp8"``: the decoder layers' projection weights are written as FP8 (e4m3fn) with
     ``fp8_scale`` (channel | tensor | block128) scales (fp8.quantize_state_dict); ``quantize="int4"``:
     as INT4 words in groups of ``int4_group`` with ``int4_scale_dtype`` scales (int4.quantize_state_dict);
     ``quantize="nf4"``: in the bitsandbytes 4-bit form, NF4 code book, blocks of ``nf4_block``, the
@@ -126,6 +129,11 @@ def write_synthetic_checkpoint(cfg: ModelConfig, out_dir: str, seed: int = 0,
     decoder layer i >= K is a hard link to layer i % K (a 138 GB 70B checkpoint in ~K x 1.7 GB of
     disk for streaming benchmarks — the reads are per file, as for a real checkpoint)."""
     os.makedirs(out_dir, exist_ok=True)
+    if score_labels:
+        import dataclasses
+        from ..classify import LAYER, synthetic_head
+        cfg = dataclasses.replace(cfg, num_labels=int(score_labels))
+        save_file(synthetic_head(cfg, seed, bias=score_bias), layer_file(out_dir, LAYER))
     cfg.save(out_dir)
     write_synthetic_tokenizer(out_dir, cfg.vocab_size)
     names = cfg.layer_names()
