@@ -160,6 +160,14 @@ int fls_attention_window(const void* qkv, void* out, const int* work, int n_item
                          int ld_kv0, const int* seg_lo, int q_block, const int* work2, const int* r2win,
                          void* ws, unsigned long long ws_bytes, int n_rows, const int* r0_lo,
                          const int* r0_item, fls_stream_t s);
+// bidirectional suffixes: fls_attention's full pass (work2 / r2win null) with a per-row upper bound on
+// range 1.  seg_hi ([T] int32): one past the last packed row of the suffix that holds the row; a row
+// sees the range-1 keys seg_lo[i] <= j < seg_hi[i], and each item's range 1 is [min seg_lo, max seg_hi)
+// of its rows.  seg_lo and seg_hi are required; q_block 64 or 128.
+int fls_attention_bidir(const void* qkv, void* out, const int* work, int n_items, int n_q_heads,
+                        int n_kv_heads, int head_dim, int ld_qkv, int ld_out, float scale, const void* kv0,
+                        int ld_kv0, const int* seg_lo, int q_block, const int* work2, const int* r2win,
+                        void* ws, unsigned long long ws_bytes, int n_rows, const int* seg_hi, fls_stream_t s);
 int fls_headnorm_rope(void* x, int ldx, int rows, int n_q, int n_k, const void* qn, const void* kn, const int* pos,
                       const float* cos_t, const float* sin_t, int hd, float eps, fls_stream_t s);
 int fls_rmsnorm(const void* x, const void* w, void* y, const int* row_idx, int rows, int H,

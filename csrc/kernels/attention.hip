@@ -15,6 +15,8 @@
 // so one item can hold several suffixes of one prompt and they all read the
 // prompt's single prefix K/V in the same pass (GQA-native: query head h uses
 // kv head h / (nh/nkv)).  Without seg_lo an item's range 1 is one suffix.
+// Bidirectional suffixes (fls_attention_bidir): key j of range 1 is visible to row i iff
+// seg_lo[i] <= j < seg_hi[i], the row's whole suffix, later keys included.
 //
 // Block: HPB query heads of one KV group x WPH waves of 32 query rows each
 // (q_block = 32 * WPH); every K/V tile staged in LDS feeds HPB * WPH waves.
@@ -116,7 +118,14 @@ __device__ __forceinline__ void lds_wait4(half4& a, half4& b, half4& c, half4& d
 // start below the max are masked per row.  Ranges 1 and 2 carry the window in seg_lo / r2win.  A
 // tile that is fully masked for a row leaves the row's m, l and O bitwise alone (mx = -inf keeps
 // m_run, P = 0), so which masked tiles an item walks does not change a row's bits.
-template <int HD, int HPB, int WPH, bool R2, bool SPL = false, bool WIN = false>
+// BID (bidirectional suffixes): range 1 of an item is [min seg_lo, max seg_hi) of its rows (the
+// packer states it in the work item) and is walked whole, whichever rows the item holds: a slice
+// of a long suffix meets every key of that suffix, the ones after its last row too.  Row i sees the
+// range-1 keys [seg_lo[i], seg_hi[i]): the upper bound is the row's own, held in registers next
+// to the lower one, where the causal kernel compares against the query index.  A wave whose rows
+// all see the whole range (one suffix in reach of the wave) masks only the range's last tile.
+// Nothing else moves: the online softmax takes a row's maximum from whichever tile holds it.
+template <int HD, int HPB, int WPH, bool R2, bool SPL = false, bool WIN = false, bool BID = false>
 __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __restrict__ qkv, half_t* __restrict__ out,
                                                     const int* __restrict__ work, const int* __restrict__ seg_lo,
                                                     int nh, int nkv, int ld_qkv, int ld_out, float scale_log2,
@@ -125,6 +134,10 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
                                                     float* __restrict__ part, const int* __restrict__ r0_lo,
                                                     const int* __restrict__ r0_item) {
   static_assert(!SPL || R2, "split-KV is built for the range-2 (suffix K/V reuse) kernel only");
+  static_assert(!BID || (!R2 && !SPL && !WIN), "bidirectional suffixes: full passes without a window only");
+  // BID has no range 2: seg_hi takes r2win's place in the argument list (an argument of its own
+  // moves the scalar loads and the register allocation of every other instantiation)
+  const int* __restrict__ seg_hi = BID ? r2win : nullptr;
   constexpr int NT_ = 64 * WPH * HPB;
   constexpr int NS = HD / 32;               // k-steps of QK^T
   constexpr int NU = HD / 16;               // 16-wide d subtiles of O
@@ -160,7 +173,8 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
   const int r_start0 = r_start0_ + shift0, r_len0 = r_len0_ - shift0, kend0 = kend0_ - shift0;
   // R2 (suffix K/V reuse): every key of a suffix, the new rows' included, is read from the cache
   // as range 2 through per-row windows, so there is no range 1
-  const int kend1 = (R2 || r_len1 <= 0) ? 0 : min(r_len1, q_off + q_len);
+  // BID: every key of the range, not only those up to the item's last query row
+  const int kend1 = (R2 || r_len1 <= 0) ? 0 : (BID ? r_len1 : min(r_len1, q_off + q_len));
   const int n0 = skip0 ? 0 : (kend0 + KT - 1) / KT;
   // R2: range 2 = rows [r_start2, r_start2 + r_len2) of kv0 (a suffix's cached K/V), all visible,
   // walked between range 0 and range 1
@@ -196,7 +210,7 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
   const int r2base = R2 ? r_start2 - r_start0 : 0;
 
   half8 qf[2][NS];
-  int qi[2], lo[2], lo2[2] = {0, 0}, hi2[2] = {0, 0};
+  int qi[2], lo[2], lo2[2] = {0, 0}, hi2[2] = {0, 0}, hi1[2] = {0, 0};
 #pragma unroll
   for (int qg = 0; qg < 2; ++qg) {
     const int qrow = rbase + qg * 16 + fr;
@@ -206,6 +220,7 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
     for (int s = 0; s < NS; ++s) qf[qg][s] = *(const half8*)(qp + s * 32);
     qi[qg] = q_off + qrow;                  // range-1 index of this query row (causal upper bound)
     lo[qg] = seg_lo && r_len1 > 0 ? seg_lo[qr] - r_start1 : 0;   // its suffix's first range-1 key
+    if constexpr (BID) hi1[qg] = r_len1 > 0 ? seg_hi[qr] - r_start1 - 1 : 0;   // ... and its last
     if constexpr (R2) {                     // its suffix's window of range 2 (relative rows)
       lo2[qg] = r2win[2 * qr] - r_start2;
       hi2[qg] = r2win[2 * qr + 1] - r_start2;
@@ -218,6 +233,8 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd(const half_t* __re
   // the whole wave iff its last key is visible to that row (range 1 with several suffixes: masked)
   const int qi_min = q_off + rbase;
   const bool multi = seg_lo != nullptr;
+  // BID: every row of the wave sees the whole of range 1 (its interior tiles then need no mask)
+  const bool whole1 = BID && __all(lo[0] == 0 && lo[1] == 0 && hi1[0] == r_len1 - 1 && hi1[1] == r_len1 - 1);
   const int live_rows = q_len - rbase;      // query rows of this wave inside the item (uniform)
 
   floatx4 o[2][NU];
@@ -296,13 +313,14 @@ _Pragma("unroll") \
     FLS_ATTN_AFTER_QK \
     /* ---- visibility: wave-uniform fast path when every key of the tile is visible to every row */ \
     /* (WIN: a causal range 0 compares against the query index behind the re-based range start) */ \
-    const int vis_last = causal ? min(klen - 1, qi_min - (WIN && !r1 ? shift0 : 0)) : klen - 1; \
-    if (k0 + KT - 1 > vis_last || (r1 && multi) || r2 || (WIN && !r1 && !r2 && k0 < lo0_all)) { \
+    /* (BID: range 1 has no causal bound; its tiles are masked by the rows' own [lo, hi1]) */ \
+    const int vis_last = causal && !(BID && r1) ? min(klen - 1, qi_min - (WIN && !r1 ? shift0 : 0)) : klen - 1; \
+    if (k0 + KT - 1 > vis_last || (r1 && (BID ? !whole1 : multi)) || r2 || (WIN && !r1 && !r2 && k0 < lo0_all)) { \
       asm volatile("" ::: "memory");        /* keep this a branch (not per-score selects on every tile) */ \
 _Pragma("unroll") \
       for (int qg = 0; qg < NQ; ++qg) { \
         /* key k0 + 16tt + 4grp + r is visible iff lo_rel <= 16tt + r <= hi_rel */ \
-        const int hi_rel = (r2 ? min(klen, hi2[qg]) - 1 : (causal ? min(klen - 1, qi[qg] - (WIN && !r1 ? shift0 : 0)) : klen - 1)) - k0 - grp * 4; \
+        const int hi_rel = (r2 ? min(klen, hi2[qg]) - 1 : (causal ? min(klen - 1, (BID && r1 ? hi1[qg] : qi[qg]) - (WIN && !r1 ? shift0 : 0)) : klen - 1)) - k0 - grp * 4; \
         const int lo_rel = (r1 ? lo[qg] : (r2 ? lo2[qg] : (WIN ? (qg ? lo0b : lo0a) : 0))) - k0 - grp * 4; \
 _Pragma("unroll") \
         for (int tt = 0; tt < 4; ++tt) \
@@ -461,6 +479,7 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd_pers(const half_t*
                                                          const half_t* __restrict__ kv0, int ld_kv0, int n_items) {
   constexpr bool R2 = false;
   constexpr bool WIN = false;               // windowed full passes take attn_fwd
+  constexpr bool BID = false;               // ... and so do passes with bidirectional suffixes
   constexpr int NT_ = 64 * WPH * HPB;
   constexpr int NS = HD / 32;
   constexpr int NU = HD / 16;
@@ -519,6 +538,8 @@ __global__ __launch_bounds__(64 * WPH * HPB, 2) void attn_fwd_pers(const half_t*
   int qi[2], lo[2];
   const int lo2[2] = {0, 0}, hi2[2] = {0, 0};
   constexpr int lo0_all = 0, lo0a = 0, lo0b = 0, shift0 = 0;
+  constexpr int hi1[2] = {0, 0};
+  constexpr bool whole1 = false;
   auto load_q = [&](const UP& p) {
     const int h = p.hg * HPB + hw;
 #pragma unroll
@@ -941,10 +962,12 @@ int launch_decode(dim3 grid, int ns, hipStream_t st, const half_t* qkv, half_t* 
   return 0;
 }
 
-template <int HD, int WPH, bool R2, bool WIN>
+template <int HD, int WPH, bool R2, bool WIN, bool BID = false>
 int launch(int hpb, dim3 grid, hipStream_t st, const half_t* qkv, half_t* out, const int* work, const int* seg_lo,
            int nh, int nkv, int ld_qkv, int ld_out, float scale_log2, const half_t* kv0, int ld_kv0,
-           const int* work2, const int* r2win, float* part, int ns, const int* r0_lo, const int* r0_item) {
+           const int* work2, const int* r2win, float* part, int ns, const int* r0_lo, const int* r0_item,
+           const int* seg_hi) {
+  if (BID && !seg_hi) return -7;
   if constexpr (R2 && HD != 96) {
     if (ns > 1) {
       const dim3 g3(grid.x, grid.y, ns);
@@ -970,8 +993,9 @@ int launch(int hpb, dim3 grid, hipStream_t st, const half_t* qkv, half_t* out, c
     }
   }
 #define FLS_ATTN_LAUNCH(HPB_)                                                                                  \
-  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, R2, false, WIN>), grid, dim3(64 * WPH * HPB_), 0, st, qkv, out, work, \
-                     seg_lo, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, r2win, nullptr, r0_lo, r0_item)
+  hipLaunchKernelGGL((attn_fwd<HD, HPB_, WPH, R2, false, WIN, BID>), grid, dim3(64 * WPH * HPB_), 0, st, qkv, out,  \
+                     work, seg_lo, nh, nkv, ld_qkv, ld_out, scale_log2, kv0, ld_kv0, work2, BID ? seg_hi : r2win,   \
+                     nullptr, r0_lo, r0_item)
   if constexpr (HD == 96) {
     FLS_ATTN_LAUNCH(1);                     // 12 chunks per row: one head per block divides the tile
   } else if constexpr (WPH == 1) {          // 4 or 8 heads (dispatch)
@@ -1060,11 +1084,11 @@ extern "C" int fls_attention_set_split(int ns) {
 }
 
 namespace {
-template <bool R2, bool WIN>
+template <bool R2, bool WIN, bool BID = false>
 int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_heads, int n_kv_heads, int head_dim,
              int ld_qkv, int ld_out, float scale, const void* kv0, int ld_kv0, const int* seg_lo, int q_block,
              const int* work2, const int* r2win, void* ws, unsigned long long ws_bytes, int n_rows,
-             fls_stream_t s, const int* r0_lo, const int* r0_item) {
+             fls_stream_t s, const int* r0_lo, const int* r0_item, const int* seg_hi = nullptr) {
   if (n_q_heads % n_kv_heads) return -2;
   if (head_dim != 64 && head_dim != 96 && head_dim != 128) return -3;
   // q_block 32 (one wave per head): range-2 items of at most 32 rows (generation steps);
@@ -1124,7 +1148,7 @@ int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_h
   auto q = (const half_t*)qkv;
   auto o = (half_t*)out;
   auto k0 = (const half_t*)kv0;
-  if constexpr (!R2 && !WIN) {              // (a windowed full pass: one block per item x head group)
+  if constexpr (!R2 && !WIN && !BID) {      // (a windowed or bidirectional-suffix full pass: one block per item x head group)
     if (g_pers && head_dim != 96 && q_block != 32)
       return q_block == 64 ? (head_dim == 128 ? launch_pers<128, 2>(hpb, n_items, st, q, o, work, seg_lo, n_q_heads,
                                                                     n_kv_heads, ld_qkv, ld_out, scale_log2, k0, ld_kv0)
@@ -1138,24 +1162,24 @@ int dispatch(const void* qkv, void* out, const int* work, int n_items, int n_q_h
   if constexpr (R2) {
     if (q_block == 32)                      // head_dim 64 / 128 here (96 fell back above)
       return head_dim == 128 ? launch<128, 1, true, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
-                                                    ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
+                                                    ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi)
                              : launch<64, 1, true, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv,
-                                                   ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
+                                                   ld_out, scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi);
   }
   if (head_dim == 96)
-    return q_block == 64 ? launch<96, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
-                         : launch<96, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
+    return q_block == 64 ? launch<96, 2, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi)
+                         : launch<96, 4, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi);
   if (q_block == 64)
-    return head_dim == 128 ? launch<128, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                            scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
-                           : launch<64, 2, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                           scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
-  return head_dim == 128 ? launch<128, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                          scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item)
-                         : launch<64, 4, R2, WIN>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
-                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item);
+    return head_dim == 128 ? launch<128, 2, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                            scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi)
+                           : launch<64, 2, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                           scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi);
+  return head_dim == 128 ? launch<128, 4, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                          scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi)
+                         : launch<64, 4, R2, WIN, BID>(hpb, grid, st, q, o, work, seg_lo, n_q_heads, n_kv_heads, ld_qkv, ld_out,
+                                         scale_log2, k0, ld_kv0, work2, r2win, part, ns, r0_lo, r0_item, seg_hi);
 }
 }  // namespace
 
@@ -1190,4 +1214,23 @@ extern "C" int fls_attention_window(const void* qkv, void* out, const int* work,
                : dispatch<false, true>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
                                        kv0, ld_kv0, seg_lo, q_block, nullptr, nullptr, nullptr, 0, 0, s, r0_lo,
                                        r0_item);
+}
+
+// Bidirectional-suffix form: fls_attention's full pass (no range 2) plus seg_hi ([rows] int32: one
+// past the last packed row of the suffix holding each row).  A row sees the prefix as before and
+// every key of its own suffix, seg_lo[i] <= j < seg_hi[i]; each item's range 1 spans
+// [min seg_lo, max seg_hi) of its rows (runtime/batch.py).  seg_lo is required.
+extern "C" int fls_attention_bidir(const void* qkv, void* out, const int* work, int n_items, int n_q_heads,
+                                   int n_kv_heads, int head_dim, int ld_qkv, int ld_out, float scale,
+                                   const void* kv0, int ld_kv0, const int* seg_lo, int q_block, const int* work2,
+                                   const int* r2win, void* ws, unsigned long long ws_bytes, int n_rows,
+                                   const int* seg_hi, fls_stream_t s) {
+  if (n_items <= 0) return 0;
+  if (work2 || r2win) return -6;              // no range 2: a suffix's cached rows are a causal notion
+  if (!seg_lo || !seg_hi) return -7;          // the per-row bounds of range 1
+  if (q_block != 64 && q_block != 128) return -5;
+  (void)ws, (void)ws_bytes, (void)n_rows;
+  return dispatch<false, false, true>(qkv, out, work, n_items, n_q_heads, n_kv_heads, head_dim, ld_qkv, ld_out, scale,
+                                      kv0, ld_kv0, seg_lo, q_block, nullptr, nullptr, nullptr, 0, 0, s, nullptr,
+                                      nullptr, seg_hi);
 }

@@ -119,7 +119,10 @@ def _load_kernels(path: str = _KERNELS):
     _bind(lib, "fls_attention_window", c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
           c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_int,
           c_void_p, c_void_p, c_void_p)
-    _bind(lib, "fls_rmsnorm", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+    _bind(lib, "fls_attention_bidir", c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+          c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_uint64, c_int,
+          c_void_p, c_void_p)
+    _bind(lib, "fls_rmsnorm",c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
           c_int, c_float, c_void_p)
     _bind(lib, "fls_headnorm_rope", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
           c_void_p, c_void_p, c_int, c_float, c_void_p)

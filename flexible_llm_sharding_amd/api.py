@@ -37,7 +37,8 @@ from .parallel.planner import make_plan
 from .runtime.stream import FileLayerSource
 from .runtime.weights import HostStore
 from .sampling import SamplingParams, draws as sample_draws, sample_tokens
-from .utils.cli import check_classify, check_embed, check_lookup, check_sampling, check_score_mode, check_top_k, parse_args
+from .utils.cli import (check_classify, check_embed, check_lookup, check_sampling, check_score_mode,
+                        check_suffix_attention, check_top_k, parse_args)
 from .utils.tokenizer import load_tokenizer
 
 
@@ -237,6 +238,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
     check_lookup(args, comm.world)
     check_embed(args, cfg.hidden_size)
     check_classify(args)
+    check_suffix_attention(args)
     mode = getattr(args, "score_mode", "next_token")
     if mode in ("loglik", "embed", "classify") and comm.world > 1 and not args.data_parallel:
         raise ValueError(f"--score_mode {mode} does not combine with model parallel: pass --data_parallel")
@@ -302,6 +304,7 @@ def build_runner(args, cfg: ModelConfig, device, comm: Comm, tok, prompts=None) 
                          pipeline_stages=getattr(args, "pipeline_stages", "round_robin"),
                          rx_window=getattr(args, "rx_window", 2),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
+                         suffix_attention=getattr(args, "suffix_attention", "causal"),
                          score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None),
                          # one rank draws the tokens on the device; several ranks: rank 0 draws the

@@ -89,9 +89,18 @@ class ShardedRunner:
                  sampling=None, score_top_k: int = 0, embed_pooling: Optional[str] = None,
                  embed_dim: Optional[int] = None, embed_normalize: Optional[bool] = None, lora=None,
                  classify_rows: Optional[str] = None, classify_activation: Optional[str] = None,
-                 classify_head=None):
+                 classify_head=None, suffix_attention: str = "causal"):
         if sliding_window_mode not in ("error", "apply"):
             raise ValueError(f"sliding_window_mode={sliding_window_mode!r}: 'error' or 'apply'")
+        # bidirectional suffixes (embedders fine-tuned without a causal mask): a suffix row sees its whole
+        # suffix.  Full embed / classify passes only: next_token and loglik rows predict the next token
+        if suffix_attention not in ("causal", "bidirectional"):
+            raise ValueError(f"--suffix_attention must be causal or bidirectional, got {suffix_attention!r}")
+        self.suffix_bidirectional = suffix_attention == "bidirectional"
+        if self.suffix_bidirectional and score_mode not in ("embed", "classify"):
+            raise ValueError(f"--suffix_attention bidirectional needs --score_mode embed or classify, not {score_mode}")
+        if self.suffix_bidirectional and sliding_window_mode == "apply":
+            raise ValueError("--suffix_attention bidirectional does not combine with --sliding_window_mode apply")
         if score_mode not in ("next_token", "loglik", "embed", "classify"):
             raise ValueError(f"score_mode={score_mode!r}: 'next_token', 'loglik' or 'embed' (or 'classify')")
         self.score_mode = score_mode
@@ -694,7 +703,7 @@ class ShardedRunner:
                                 suffix_keep=[sfx_keep[i] for i in g] if sfx_keep is not None else None,
                                 single_suffix_items=self.row_exact, window=window, loglik=self.loglik,
                                 score_rows=[score_rows[i] for i in g] if score_rows is not None else None,
-                                pool=pool)
+                                pool=pool, suffix_bidirectional=self.suffix_bidirectional)
                    for g in groups]
         if drafts is not None:
             for b, g in zip(batches, groups):

@@ -446,6 +446,8 @@ def _attention_whole(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Tens
     if work_items and "work2" in meta:       # suffix K/V reuse: range 2 = the suffixes' kept rows
         kw["work2"] = meta["work2_last"] if prune else meta["work2"]
         kw["r2win"] = meta["r2win"]
+    if work_items and "seg_hi" in meta and not prune:   # bidirectional suffixes (the pruned layer's
+        kw["seg_hi"] = meta["seg_hi"]                   # rows, each suffix's last, see the same keys causally)
     if work_items and "r0_lo" in meta:       # sliding window: per-row / per-item range-0 bounds
         kw["r0_lo"] = meta["r0_lo"]
         kw["r0_item"] = meta["r0_item_last"] if prune else meta["r0_item"]
@@ -494,6 +496,8 @@ def _attention_grouped(ctx: ExecContext, W: Dict[str, torch.Tensor], x: torch.Te
         else:
             arg = g["work"] if work_items else g["segments"]
         kw = {"seg_lo": g["seg_lo"]} if work_items else {}
+        if work_items and "seg_hi" in g and not prune:   # bidirectional suffixes
+            kw["seg_hi"] = g["seg_hi"]
         if work_items and "r0_lo" in g:      # sliding window
             kw["r0_lo"] = g["r0_lo"]
             kw["r0_item"] = g["r0_item_last"] if prune else g["r0_item"]

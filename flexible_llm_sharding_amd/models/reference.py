@@ -145,9 +145,10 @@ def reference_logliks(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompt
 def reference_embeddings(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence,
                          pooling: str = "last", dim: int = 0, normalize: bool = True,
                          prefix_attention: str = "bidirectional", max_len: int = 4096,
-                         cos=None, sin=None) -> List[np.ndarray]:
+                         cos=None, sin=None, suffix_attention: str = "causal") -> List[np.ndarray]:
     """Per prompt a float32 [n_s, D] array: each suffix's pooled final-norm hidden state (embed.py),
-    from the forward of :func:`reference_scores`.  ``pooling="last"``: the final-norm row of the
+    from the forward of :func:`reference_scores` (``suffix_attention="bidirectional"``: a suffix token
+    sees every real token of its own suffix, later ones too).  ``pooling="last"``: the final-norm row of the
     suffix's last real token; ``"mean"``: the mean of the final-norm rows of its real tokens;
     ``dim`` (0: H): the first D columns; ``normalize``: divided by max(L2 norm, 1e-12)."""
     if pooling not in ("last", "mean"):
@@ -156,7 +157,7 @@ def reference_embeddings(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, pro
     if not 1 <= D <= cfg.hidden_size:
         raise ValueError(f"dim={dim}")
     outs = []
-    for P, S, sids, eos in _forward(cfg, sd, tok, prompts, prefix_attention, max_len, cos, sin):
+    for P, S, sids, eos in _forward(cfg, sd, tok, prompts, prefix_attention, max_len, cos, sin, suffix_attention):
         Y = _rms(S, sd["model.norm.weight"].float(), cfg.rms_norm_eps)             # [ns, Ls, H]
         rows = []
         for s in range(sids.shape[0]):
@@ -172,7 +173,7 @@ def reference_embeddings(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, pro
 
 
 def _forward(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequence, prefix_attention: str,
-             max_len: int, cos, sin):
+             max_len: int, cos, sin, suffix_attention: str = "causal"):
     """Per prompt: (prefix hidden states [1, Lp, H], suffix hidden states [n_s, Ls, H] after the
     last decoder layer, the padded suffix ids [n_s, Ls], the reference's suffix_eos [n_s])."""
     from .llama import rope_tables
@@ -201,6 +202,13 @@ def _forward(cfg: ModelConfig, sd: Dict[str, torch.Tensor], tok, prompts: Sequen
             band = torch.full((Lp, Lp), neg).tril(-W)[None, None]
             pmask = band if pmask is None else torch.minimum(pmask, band)
         smask = full[-Ls:, -(Lp + Ls):][None, None].expand(ns, 1, Ls, Lp + Ls)   # utils.py:276
+        if suffix_attention == "bidirectional":
+            # the whole prefix and every real token of the row's own suffix (the padding stays hidden)
+            if cfg.sliding_window and Lp + Ls > int(cfg.sliding_window):
+                raise ValueError("suffix_attention='bidirectional' is not defined under a sliding window")
+            pad = torch.arange(Ls)[None, :] > eos[:, None]                           # [ns, Ls]
+            smask = torch.zeros(ns, 1, Ls, Lp + Ls)
+            smask[:, 0, :, Lp:] = torch.where(pad, neg, 0.0)[:, None, :]
         for i in range(cfg.num_hidden_layers):
             p = f"model.layers.{i}"
             P, (kc, vc) = _block(P, sd, p, cfg, ppos, cos, sin, pmask)

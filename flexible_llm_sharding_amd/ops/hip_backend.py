@@ -414,7 +414,7 @@ class HipOps:
 
     # ----------------------------------------------------------- attention
     def attention(self, qkv, work, n_q_heads, n_kv_heads, head_dim, kv0=None, q_block: int = 64, out=None,
-                  seg_lo=None, work2=None, r2win=None, scale=None, r0_lo=None, r0_item=None):
+                  seg_lo=None, work2=None, r2win=None, scale=None, r0_lo=None, r0_item=None, seg_hi=None):
         """kv0 ([P, 2 * n_kv * hd], K then V): range 0 of every work item reads these rows (prefix cache).
         seg_lo ([T] int32, first row of each row's suffix): work items may span several suffixes.
         work2 ([n_items, 2] int32: r2_start, r2_len) + r2win ([T, 2] int32: kv0 rows [lo, hi) per row):
@@ -422,7 +422,9 @@ class HipOps:
         walked between the prefix and the new rows, each row seeing its own suffix's window.
         r0_lo ([T] int32: first range-0 key each row sees, relative to the range start) + r0_item
         ([n_items, 2] int32: its min and max over each item's rows): sliding-window attention
-        (PackedBatch.r0_lo / r0_item; seg_lo and r2win then carry the window of ranges 1 and 2)."""
+        (PackedBatch.r0_lo / r0_item; seg_lo and r2win then carry the window of ranges 1 and 2).
+        seg_hi ([T] int32, one past the last row of each row's suffix; PackedBatch.seg_hi): bidirectional
+        suffixes, a row sees the range-1 keys seg_lo[i] <= j < seg_hi[i] (full passes: no work2, no window)."""
         _f16(qkv, "qkv")
         if work.dtype != torch.int32 or not work.is_cuda:
             raise TypeError("work items must be an int32 CUDA tensor")
@@ -446,6 +448,14 @@ class HipOps:
                                   or r0_item.dtype != torch.int32 or not r0_item.is_cuda
                                   or tuple(r0_item.shape) != (work.shape[0], 2) or not r0_item.is_contiguous()):
             raise TypeError("r0_lo must be int32 CUDA [T] with r0_item int32 CUDA [n_items, 2]")
+        if seg_hi is not None:
+            if (seg_hi.dtype != torch.int32 or not seg_hi.is_cuda or seg_hi.dim() != 1 or seg_hi.shape[0] < T
+                    or not seg_hi.is_contiguous()):
+                raise TypeError("seg_hi (PackedBatch.seg_hi) must be int32 CUDA [T]")
+            if work2 is not None or r0_lo is not None or kv0 is not None:
+                raise ValueError("seg_hi (bidirectional suffixes) does not combine with work2, r0_lo or kv0")
+            if q_block not in (64, 128):
+                raise ValueError(f"seg_hi (bidirectional suffixes): q_block 64 or 128, got {q_block}")
         if out is None:
             out = torch.empty(T, n_q_heads * head_dim, dtype=torch.float16, device=qkv.device)
         # the range-2 (decode-like) kernel splits its key tiles over blocks when the grid is small;
@@ -462,7 +472,9 @@ class HipOps:
                 work2.data_ptr() if work2 is not None else None,
                 r2win.data_ptr() if work2 is not None else None,
                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, T)
-        if r0_lo is not None:
+        if seg_hi is not None:
+            rc = self.k.fls_attention_bidir(*args, seg_hi.data_ptr(), _stream())
+        elif r0_lo is not None:
             rc = self.k.fls_attention_window(*args, r0_lo.data_ptr(), r0_item.data_ptr(), _stream())
         else:
             rc = self.k.fls_attention(*args, _stream())

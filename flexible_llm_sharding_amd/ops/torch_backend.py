@@ -171,7 +171,8 @@ class TorchOps:
             if getattr(sg, "r2_len", 0):        # suffix K/V reuse: the suffix's kept rows, all visible
                 kr.append((sg.r2_start, sg.r2_len, 0, k0_all, v0_all))
             if sg.r1_len:
-                kr.append((sg.r1_start, sg.r1_len, 1, k_all, v_all))
+                # (bidirectional suffixes: the segment is one suffix, every key of it visible)
+                kr.append((sg.r1_start, sg.r1_len, 0 if getattr(sg, "r1_bidir", 0) else 1, k_all, v_all))
             ks_, vs_, masks = [], [], []
             qi = torch.arange(sg.q_len, device=dev) + sg.q_off
             for st, ln, causal, kk, vv in kr:

@@ -376,6 +376,7 @@ def build_dp_sharded_runner(args, cfg, device, comm: Comm, tok, store: Optional[
                          prefix_cache_entries=getattr(args, "prefix_cache_entries", 8),
                          suffix_kv_cache=_suffix_kv(args, comm), exact_reuse=getattr(args, "exact_reuse", True),
                          sliding_window_mode=getattr(args, "sliding_window_mode", "error"),
+                         suffix_attention=getattr(args, "suffix_attention", "causal"),
                          score_mode=getattr(args, "score_mode", "next_token"),
                          max_vram_gb=getattr(args, "max_vram_gb", None),
                          score_top_k=int(getattr(args, "score_top_k", 0) or 0), lora=lora, **embed_kw)

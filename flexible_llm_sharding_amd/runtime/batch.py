@@ -49,13 +49,14 @@ class Segment:
     r0_len: int
     r0_causal: int
     r1_start: int
-    r1_len: int          # r1 (own suffix) is always causal
+    r1_len: int          # r1 (own suffix) is causal unless r1_bidir
     q_off: int = 0       # index of the first query inside its segment (causal compare)
     r2_start: int = 0    # suffix K/V reuse: rows of the K/V cache holding this suffix's earlier
     r2_len: int = 0      # tokens (all visible), between the prefix (r0) and the new rows (r1)
     window: int = 0      # sliding window W > 0: a key at model position j is visible to a query at
                          # position i only if i - j < W (prefix token p: position p; token s of a
                          # suffix: r0_len + s, kept rows included); the window only cuts off the past
+    r1_bidir: int = 0    # bidirectional suffixes: every key of r1 is visible to every query of the segment
 
 
 # range-2 (generation-step) attention items of <= 8 rows: the packed-GQA decode kernel
@@ -109,6 +110,8 @@ class PackedBatch:
                                                 # scored row, -1 on a suffix's last (ops.verify_rows)
     seg_start: Optional[np.ndarray] = None      # pooled embeddings (``pack_prompts(pool=...)``): [n_sfx + 1]
                                                 # int32, each suffix's range of ``last_idx`` (ops.pool_rows)
+    seg_hi: Optional[np.ndarray] = None         # bidirectional suffixes: [T] int32, one past the last packed
+                                                # row of each row's suffix (prefix rows: of the prefix)
     _dev: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -169,6 +172,7 @@ class PackedBatch:
                         "work": self._rebase(self.work[w0:w1], r0),
                         "work_last": self._rebase(self.work_last[s0:s1], r0),
                         "seg_lo": (self.seg_lo[r0:r1] - r0).astype(np.int32),
+                        **({} if self.seg_hi is None else {"seg_hi": (self.seg_hi[r0:r1] - r0).astype(np.int32)}),
                         "last_local": (self.last_idx[s0:s1] - r0).astype(np.int32),
                         "last_pos": self.positions[self.last_idx[s0:s1]].astype(np.int32)})
         return out
@@ -209,7 +213,7 @@ class PackedBatch:
              "last_idx": self.last_idx, "last_pos": self.positions[self.last_idx].astype(np.int32),
              "work_last": self.work_last}
         for name in ("pfx_src", "pfx_dst", "sfx_src", "sfx_dst", "work2", "work2_last", "r2win",
-                     "r0_lo", "r0_item", "r0_item_last", "targets", "row_start", "draft", "seg_start"):
+                     "r0_lo", "r0_item", "r0_item_last", "targets", "row_start", "draft", "seg_start", "seg_hi"):
             v = getattr(self, name)
             if v is not None:
                 m[name] = v
@@ -232,7 +236,8 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                  suffix_rows: Optional[Sequence[Sequence[int]]] = None,
                  suffix_keep: Optional[Sequence[Sequence[int]]] = None,
                  single_suffix_items: bool = False, window: int = 0, loglik: bool = False,
-                 score_rows: Optional[Sequence[Sequence[int]]] = None, pool: Optional[str] = None) -> PackedBatch:
+                 score_rows: Optional[Sequence[Sequence[int]]] = None, pool: Optional[str] = None,
+                 suffix_bidirectional: bool = False) -> PackedBatch:
     """Pack prompts into one token matrix + attention work items.
 
     ``prefix_offsets`` (rows of each prompt's prefix in a PrefixEntry) turns on
@@ -278,7 +283,19 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     ``"mean"``: ``last_idx`` holds every row of every suffix, in row order (``prompt_scored`` ranges
     over them; ``last_segments`` / ``work_last`` stay per suffix: such a batch runs the unpruned last
     layer, which reads neither); every suffix needs a token; not with ``kv_cached`` / ``suffix_keep``.
+
+    ``suffix_bidirectional``: a suffix row sees every key of its own suffix, the later ones too
+    (and the prefix as before; never another suffix).  ``seg_hi`` then holds one past the last row
+    of each row's suffix, and range 1 of a work item is ``[min seg_lo, max seg_hi)`` of its rows:
+    an item holding a slice of a long suffix walks the whole suffix.  ``work_last`` and
+    ``last_segments`` stay as they are: a suffix's last row sees its whole suffix under either
+    rule.  Full passes only: not with ``window``, ``kv_cached``, ``suffix_keep``, ``loglik`` or
+    ``score_rows``.  False is the packing without it, byte for byte.
     """
+    bidir = bool(suffix_bidirectional)
+    if bidir and (window or kv_cached or suffix_keep is not None or loglik or score_rows is not None):
+        raise ValueError("suffix_bidirectional does not combine with window, kv_cached, suffix_keep, loglik "
+                         "or score_rows")
     if pool not in (None, "last", "mean"):
         raise ValueError(f"pool={pool!r}")
     if pool is not None and (loglik or (score_rows is not None and pool != "last")):
@@ -301,6 +318,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
     # per-row arrays are gathered as numpy parts (one per prefix / suffix) and concatenated once:
     # Python lists of 43k ints cost the host ~10 ms per call (the GPU idles at the call boundary)
     ids, pos, seg_lo, segs, last, nsuf, lsegs = [], [], [], [], [], [], []
+    seg_hi = []
     if suffix_keep is not None and not kv_cached:
         raise ValueError("suffix K/V reuse needs the prefix K/V cache (kv_cached)")
     if suffix_keep is not None and any(r < 0 for rows in suffix_rows for r in rows):
@@ -326,6 +344,8 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             pos.append(np.arange(Lp, dtype=np.int32))
             segs.append(Segment(p0, Lp, p0, Lp, pcausal, 0, 0, window=W))
             seg_lo.append(np.full(Lp, p0, dtype=np.int32))
+            if bidir:
+                seg_hi.append(np.full(Lp, p0 + Lp, dtype=np.int32))
             work.extend(_items(segs[-1], q_block))
             work2.extend([(0, 0)] * (len(work) - len(work2)))
             if W:
@@ -338,6 +358,7 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             t += Lp
         sfx0, lo_parts0 = t, len(r0_lo)
         sfx_lo = []                    # seg_lo of this prompt's suffix rows (row - sfx0)
+        sfx_hi = []                    # bidirectional suffixes: seg_hi of the same rows
         sfx_of = []                    # index of the suffix holding each of them
         keep = suffix_keep[j] if suffix_keep is not None else None
         for si, s in enumerate(tp.suffixes):
@@ -354,12 +375,15 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
             seg_lo.append(np.maximum(np.arange(s0, s0 + n, dtype=np.int32) - (W - 1), s0) if W
                           else np.full(n, s0, dtype=np.int32))
             sfx_lo.extend([s0] * n)
+            if bidir:
+                sfx_hi.extend([s0 + n] * n)
+                seg_hi.append(np.full(n, s0 + n, dtype=np.int32))
             sfx_of.extend([si] * n)
             if W:
                 r0_lo.append(np.clip(np.arange(Lp + c, Lp + c + n, dtype=np.int32) - (W - 1), 0, Lp))
                 r0_item_last.extend((int(v),) * 2 for v in r0_lo[-1][n - k_sc:])
             r2s, r2l = (c0_row, c) if c else (0, 0)
-            segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l, window=W))
+            segs.append(Segment(s0, n, p0, Lp, 0, s0, n, r2_start=r2s, r2_len=r2l, window=W, r1_bidir=int(bidir)))
             last.extend(range(s0 + n - k_sc, s0 + n))
             if loglik:
                 if n == 0:
@@ -417,7 +441,9 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
                 work2.append((lo, hi - lo))
             else:
                 r1 = sfx_lo[c0 - sfx0]
-                work.append((c0, c1 - c0, c0 - r1, p0, Lp, 0, r1, c1 - r1))
+                # (bidirectional suffixes: up to the end of the suffix holding the chunk's last row)
+                r1e = sfx_hi[c1 - 1 - sfx0] if bidir else c1
+                work.append((c0, c1 - c0, c0 - r1, p0, Lp, 0, r1, r1e - r1))
                 work2.append((0, 0))
             if W:
                 rl = sfx_r0[c0 - sfx0:c1 - sfx0]
@@ -460,7 +486,8 @@ def pack_prompts(tps: Sequence[TokenizedPrompt], prompt_ids: Sequence[int],
         r0_lo=cat(r0_lo) if W else None,
         r0_item=np.asarray(r0_item, dtype=np.int32).reshape(-1, 2) if W else None,
         r0_item_last=np.asarray(r0_item_last, dtype=np.int32).reshape(-1, 2) if W else None,
-        targets=cat(pair_tgt) if loglik else None, seg_start=seg_start)
+        targets=cat(pair_tgt) if loglik else None, seg_start=seg_start,
+        seg_hi=cat(seg_hi) if bidir else None)
 
 
 def _items(sg: Segment, q_block: int = Q_BLOCK) -> List[tuple]:
@@ -478,7 +505,7 @@ def _work_items(segs: Sequence[Segment], q_block: int = Q_BLOCK) -> np.ndarray:
 
 def visible_keys(work: np.ndarray, seg_lo: Optional[np.ndarray], row: int,
                  work2: Optional[np.ndarray] = None, r2win: Optional[np.ndarray] = None,
-                 r0_lo: Optional[np.ndarray] = None) -> List[tuple]:
+                 r0_lo: Optional[np.ndarray] = None, seg_hi: Optional[np.ndarray] = None) -> List[tuple]:
     """(range, first key row, last key row) visible to packed query ``row`` under the work items:
     the semantics of the attention kernel (csrc/kernels/attention.hip), for host-side tests."""
     for it, (q_start, q_len, q_off, r0s, r0l, r0c, r1s, r1l) in enumerate(work.tolist()):
@@ -498,7 +525,8 @@ def visible_keys(work: np.ndarray, seg_lo: Optional[np.ndarray], row: int,
                     out.append((2, lo, hi - 1))
             if r1l > 0:
                 lo = (int(seg_lo[row]) - r1s) if seg_lo is not None else 0
-                out.append((1, r1s + lo, r1s + min(r1l - 1, qi)))
+                # (bidirectional suffixes: up to the row's own seg_hi instead of the query index)
+                out.append((1, r1s + lo, r1s + min(r1l - 1, qi if seg_hi is None else int(seg_hi[row]) - r1s - 1)))
             return out
     return []
 

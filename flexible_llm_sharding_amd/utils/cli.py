@@ -50,6 +50,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_gpus", type=int, default=None, help="GPUs to use (default: all visible; 0 = CPU)")
     p.add_argument("--prefix_attention", choices=["bidirectional", "causal"], default="bidirectional",
                    help="prefix self-attention: reference-compatible bidirectional (default) or causal")
+    p.add_argument("--suffix_attention", choices=["causal", "bidirectional"], default="causal",
+                   help="suffix self-attention, with --score_mode embed or classify: causal (default), or "
+                        "bidirectional for embedders and rerankers fine-tuned without a causal mask (a suffix "
+                        "token then sees every token of its own suffix, later ones too, and the prefix as "
+                        "--prefix_attention decides; prefix tokens still see no suffix).  Not with --score_mode "
+                        "next_token or loglik, nor with --sliding_window_mode apply")
     p.add_argument("--sliding_window_mode", choices=["error", "apply"], default="error",
                    help="models with a sliding window (Mistral, Mixtral, Phi-3, Qwen with use_sliding_window) and a "
                         "prompt longer than it: error (default) refuses the call; apply runs sliding-window "
@@ -264,6 +270,23 @@ def check_classify(args) -> None:
             raise ValueError(f"--score_mode classify does not combine with {flag}")
 
 
+def check_suffix_attention(args) -> None:
+    """``--suffix_attention bidirectional``: with ``--score_mode embed`` or ``classify`` only (the rows
+    of ``next_token`` and ``loglik`` predict the next token and must not see it), and not with
+    ``--sliding_window_mode apply``; a ``ValueError`` names the flag.  What embed and classify refuse
+    stays refused by their own checks."""
+    v = getattr(args, "suffix_attention", "causal")
+    if v not in ("causal", "bidirectional"):
+        raise ValueError(f"--suffix_attention must be causal or bidirectional, got {v!r}")
+    if v == "causal":
+        return
+    mode = getattr(args, "score_mode", "next_token")
+    if mode not in ("embed", "classify"):
+        raise ValueError(f"--suffix_attention bidirectional needs --score_mode embed or classify, not {mode}")
+    if getattr(args, "sliding_window_mode", "error") == "apply":
+        raise ValueError("--suffix_attention bidirectional does not combine with --sliding_window_mode apply")
+
+
 def check_lora(args) -> None:
     """``--lora`` / ``--lora_scale``: one adapter directory, no scale without an adapter, and no
     adapter on ``--synthetic`` weights; a ``ValueError`` names the flag."""
@@ -342,6 +365,7 @@ def parse_args(argv=None):
     check_score_mode(args)
     check_embed(args)
     check_classify(args)
+    check_suffix_attention(args)
     check_sampling(args)
     check_top_k(args)
     check_lookup(args)

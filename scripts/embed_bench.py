@@ -73,7 +73,7 @@ def pass_bench(a) -> None:
         r = ShardedRunner(cfg, store, dev, tok, **kw)
     else:
         r = ShardedRunner(cfg, store, dev, tok, score_mode="embed", embed_pooling="last" if m == "embed_last" else "mean",
-                          **kw)
+                          suffix_attention=a.suffix_attention, **kw)
         if m == "embed_mean_pruned":
             r.set_mean_variant(True)
     times = []
@@ -87,7 +87,7 @@ def pass_bench(a) -> None:
         if i >= a.warmup:
             times.append(dt)
         print(f"[embed_bench] step {i} {m}: {dt:.3f}s d2h={r.score_d2h_bytes} plan={r.vram_plan}", flush=True)
-    res = {"mode": m, "median_s": float(np.median(times)), "min_s": min(times), "max_s": max(times), "n": len(times),
+    res = {"mode": m, "suffix_attention": a.suffix_attention, "median_s": float(np.median(times)), "min_s": min(times), "max_s": max(times), "n": len(times),
            "score_d2h_bytes": r.score_d2h_bytes, "plan": r.vram_plan,
            "config": {"model": a.model, "layers": cfg.num_hidden_layers, "prompts": 32, "tokens": 32 * (1024 + 320),
                       "suffix_rows": 32 * 320, "max_vram_gb": a.max_vram_gb}}
@@ -102,6 +102,7 @@ if __name__ == "__main__":
     ap.add_argument("what", choices=["kernel", "pass"])
     ap.add_argument("--mode", choices=["next_token", "embed_last", "embed_mean", "embed_mean_pruned"],
                     default="embed_last")
+    ap.add_argument("--suffix-attention", choices=["causal", "bidirectional"], default="causal", help="pass, embed modes")
     ap.add_argument("--save", default=None, help="pass: write the embeddings here (.npy)")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--steps", type=int, default=3)
